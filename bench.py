@@ -4,10 +4,20 @@
 A "step" = one pass of the vote path over one batch of synthetic reads, measured as
 SURVEY.md §8(d) defines the metric: from 2-bit packed reads resident in host-pinned
 memory to mapping_result_t[3] per read end in host memory (svg_vote_batch_packed:
-PCIe both ways included; reads are packed once, before timing).  Secondary fields:
-the same kernels with reads and records already in HBM (device_path,
-svg_vote_batch_device) and the ASCII host entry point (svg_vote_batch).  Workloads
-(SURVEY.md §8(d)):
+PCIe both ways included; reads are packed once, before timing).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that figure needs: it
+builds the index, simulates and packs the reads, runs W warmup and N timed steps, and prints the
+result line (metric, value, unit, ms_per_step, config, host_step_ms).  `--dump-outputs DIR`
+also writes the records of the last timed step (a fixed seeded sample of the reads, all of
+them when they fit) as DIR/<name>.npy in float64, one column per scalar of the record; the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
+`--full` adds everything else to the line, each measured outside the timed region in runs of
+its own: the per-kernel HIP-event times and the roofline figures, the same kernels with reads
+and records already in HBM (device_path, svg_vote_batch_packed_device), the ASCII host entry
+point (svg_vote_batch), sublong's voting step, the parity check against the oracle and the
+CPU baselines.  Workloads:
   c3g: C3 with the gapped index (gap 3, the reference's default index type).
   c2: 10M x 100 bp SE reads per GPU vs a chr901-scale 1,000,000 bp
       i.i.d. genome (seed 901), full one-block index (subread-buildindex -F -B),
@@ -161,11 +171,58 @@ def committed_fracs(wl, kernel, bytes_per_launch):
     return out
 
 
+DUMP_BUDGET = 48 << 20   # bytes of --dump-outputs files in all (the limit is 64 MB)
+DUMP_SEED = 20261019
+
+
+def records_as_float(a):
+    """A record array of shape S as float64 of shape S + (columns,): one column per scalar of
+    the record in field order, sub-arrays flattened, padding fields included (the caller receives
+    them too).  No field is wider than 32 bits, so float64 holds every value exactly."""
+    a = np.asarray(a)
+    if a.dtype.names is None:
+        return a.astype(np.float64)
+    cols = []
+    for name in a.dtype.names:
+        assert a.dtype[name].base.itemsize <= 4, name
+        cols.append(a[name].astype(np.float64).reshape(a.shape + (-1,)))
+    return np.concatenate(cols, axis=-1)
+
+
+def dump_sample(n, row_bytes, budget=DUMP_BUDGET, seed=DUMP_SEED):
+    """The reads whose records --dump-outputs writes: all n when they fit the budget, else a fixed
+    seeded sample of them in ascending order (the same for every run with the same arguments)."""
+    m = min(n, max(1, budget // row_bytes))
+    if m == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> array whose first axis is the read (pair) of the step.  Writes
+    dirname/<name>.npy (float64, the sampled reads) and dirname/sample_index.npy (their indices)."""
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    n = len(next(iter(arrays.values())))
+    cols = sum(records_as_float(v[:1]).size for v in arrays.values())
+    idx = dump_sample(n, 8 * (cols + 1))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "sample_index.npy"), idx.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), records_as_float(v[idx]))
+    return len(idx)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure (per-kernel and roofline "
+                         "figures, HBM-resident and ASCII paths, sublong, parity check, CPU baselines); the options "
+                         "below that shape those legs apply only with it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the records of the last timed step (a fixed seeded sample) as DIR/<name>.npy")
     ap.add_argument("--workload", default=os.environ.get("SVG_WORKLOAD", "c3"))
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step (default: workload size)")
     ap.add_argument("--workdir", default=os.environ.get("SVG_BENCH_DIR", ""))
@@ -186,6 +243,10 @@ def main():
     ap.add_argument("--kernel-record", default="",
                     help="also write the timing step's per-kernel HIP-event table and the step times here (JSON)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.kernel_record and not args.full:
+        ap.error("--kernel-record needs --full (the per-kernel timing step is one of its legs)")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -241,10 +302,10 @@ def main():
         prefix_cpu = prefix
     else:
         # 3 Gbp: build the same index straight into this GPU's HBM (replicated per rank); rank 0 of an
-        # N=1 run also writes it to reference-format files for the reference's timed CPU run
+        # N=1 --full run also writes it to reference-format files for the reference's timed CPU run
         t1 = time.time()
         gap = W.get("gap", 1)
-        if rank == 0 and world == 1 and not args.no_cpu and os.path.exists(ref_binary(W["kind"])):
+        if args.full and rank == 0 and world == 1 and not args.no_cpu and os.path.exists(ref_binary(W["kind"])):
             prefix_cpu = os.path.join(wd, "index_%s" % args.workload)
         ix = sa.VoteIndex.build_genome(genome, gap=gap, memory_mb=8000, force_one_block=gap == 1, device=device,
                                        save_prefix=prefix_cpu)
@@ -314,12 +375,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
-    # per-kernel times: one more host step with per-launch HIP events (recorded by the library on
-    # each launch's stream), outside the timed region -- folding the event ring synchronises
-    ix.set_timing(True)
-    host_step()
-    kt = ix.kernel_timing()
-    ix.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in the caller's record buffers, before any other leg runs
+        t1 = time.time()
+        kept = dump_outputs(args.dump_outputs, {"mapping": out, "subjunc": jout, "big_margin": bmo})
+        log("[bench] wrote the records of %d of %d %s to %s in %.1fs" % (
+            kept, n, "pairs" if ends == 2 else "reads", args.dump_outputs, time.time() - t1))
+    if args.full:
+        # per-kernel times: one more host step with per-launch HIP events (recorded by the library on
+        # each launch's stream), outside the timed region -- folding the event ring synchronises
+        ix.set_timing(True)
+        host_step()
+        kt = ix.kernel_timing()
+        ix.set_timing(False)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -327,6 +395,39 @@ def main():
     step_ms = [round((b - a) * 1e3, 1) for a, b in zip([t_start] + step_ends[:-1], step_ends)]
     log("[bench] packed host path: %.1f Mreads/s (%.1f ms/step; steps %s ms)" % (
         n * ends * args.steps / elapsed / 1e6, elapsed / args.steps * 1e3, step_ms))
+    total_reads = n * ends * world * args.steps
+    value = total_reads / elapsed / 1e6
+    line = {
+        "metric": METRIC, "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic",
+        "config": {"workload": W["desc"], "reads_per_gpu_per_step": n * ends, "read_len": L,
+                   "mode": {"se": "subread-align SE", "pe": "subread-align PE", "sj": "subjunc SE",
+                            "sjpe": "subjunc PE"}[kind],
+                   "entry": "svg_vote_batch_packed: 2-bit packed reads in host-pinned memory -> mapping_result_t "
+                            "in host-pinned memory (H2D + vote + compacted D2H + host expansion)",
+                   "index": "%s one-block (gap %d), %d buckets, %d items, %s" % (
+                       "full" if ix.info.index_gap == 1 else "gapped", ix.info.index_gap, ix.info.buckets, ix.info.items,
+                       "reference-format files via svg_index_open" if prefix else "built in HBM by svg_index_build_mem"),
+                   "parallelism": "reads sharded across %d GPU(s), index replicated, no collective" % world,
+                   "host_threads_per_rank": int(sa.lib().svg_host_threads()),
+                   "host_placement": {"gpu_numa_node": placement[0], "usable_cpus_on_node": placement[1],
+                                      "pinned_pages": "svg_host_alloc: preferred node %d" % placement[0]
+                                      if placement[0] >= 0 else "svg_host_alloc: node unknown (default policy)",
+                                      "expansion_workers": "pinned to the node's CPUs" if placement[1] > 0
+                                      else "unpinned (no usable CPU on the node)"}},
+        "host_step_ms": step_ms,
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        del keep
+        ix.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- secondary: the same kernels with the same 2-bit packed reads and the records already in
     # HBM (svg_vote_batch_packed_device: no PCIe, no host expansion)
@@ -595,29 +696,9 @@ def main():
             cpu_base["port"] = port
         else:
             cpu_base.update(port)
-    total_reads = n * ends * world * args.steps
-    value = total_reads / elapsed / 1e6
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": round(value, 3), "unit": "Mreads/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic",
-            "config": {"workload": W["desc"], "reads_per_gpu_per_step": n * ends, "read_len": L,
-                       "mode": {"se": "subread-align SE", "pe": "subread-align PE", "sj": "subjunc SE",
-                                "sjpe": "subjunc PE"}[kind],
-                       "entry": "svg_vote_batch_packed: 2-bit packed reads in host-pinned memory -> mapping_result_t "
-                                "in host-pinned memory (H2D + vote + compacted D2H + host expansion)",
-                       "index": "%s one-block (gap %d), %d buckets, %d items, %s" % (
-                           "full" if ix.info.index_gap == 1 else "gapped", ix.info.index_gap, ix.info.buckets, ix.info.items,
-                           "reference-format files via svg_index_open" if prefix else "built in HBM by svg_index_build_mem"),
-                       "parallelism": "reads sharded across %d GPU(s), index replicated, no collective" % world,
-                       "host_threads_per_rank": int(sa.lib().svg_host_threads()),
-                       "host_placement": {"gpu_numa_node": placement[0], "usable_cpus_on_node": placement[1],
-                                          "pinned_pages": "svg_host_alloc: preferred node %d" % placement[0]
-                                          if placement[0] >= 0 else "svg_host_alloc: node unknown (default policy)",
-                                          "expansion_workers": "pinned to the node's CPUs" if placement[1] > 0
-                                          else "unpinned (no usable CPU on the node)"}},
+        del line["host_step_ms"]        # keeps its place after the roofline block
+        line.update({
             "roofline": {"bound": bound, "regime": kernels[dom]["regime"], "kernel": dom, "achieved": round(vote_achieved, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(vote_achieved / HBM_PEAK_GBS, 5),
                          "traffic": traffic, "traffic_unit": "GB per launch",
@@ -635,7 +716,7 @@ def main():
             "sublong_voting": long_fig,
             "cpu_baseline": cpu_base,
             "parity_check": check,
-        }
+        })
         print(json.dumps(line), flush=True)
     del keep
     ix.close()

@@ -26,7 +26,7 @@ def test_bench_two_ranks(tmp_path):
     env = dict(os.environ, SVG_BENCH_DIR=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2",
            "--reads", "2000000", "--no-cpu", "--ascii-reads", "0", "--device-steps", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=560, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-5000:]

@@ -7,7 +7,7 @@ Usage:
 
 Each DIR is a rocprofv3 output directory (run_results.db, or *_counter_collection.csv).
 The vote kernel's first dispatch is the timed-configuration launch (bench.py
---steps 1 --warmup 0); later dispatches are bench.py's stats pass and are
+--full --steps 1 --warmup 0); later dispatches are its stats pass and are
 reported but not used.
 
 Units and corrections (MI355X_MICROARCH.md, "HBM" and "rocprofv3 PMC slots"):
@@ -96,7 +96,7 @@ def main():
     w = per_dispatch(rows(a.write), kern, "WRITE_SIZE")
     assert f and w, "no vote_kernel dispatches in the PMC passes"
     kname = "probe_kernel + " + [k for k, n, *_ in rows(a.fetch) if k.startswith(kern)][0]
-    # bench.py --steps 1 --warmup 0 runs the timed step, then the stats pass: half the
+    # bench.py --full --steps 1 --warmup 0 runs the timed step, then the stats pass: half the
     # dispatches of each kernel belong to the timed step
     nd = max(1, len(f) // 2)
     fetch_b = step_total(rows(a.fetch), "FETCH_SIZE", nd) * 1024.0
@@ -134,14 +134,14 @@ def main():
     if a.md:
         L = ["# rocprofv3 summary — %s (%s)" % (a.workload, kname), ""]
         if a.stats:
-            L += ["## `rocprofv3 --kernel-trace --stats` (bench.py --steps 3 --warmup 1)", "",
+            L += ["## `rocprofv3 --kernel-trace --stats` (bench.py --full --steps 3 --warmup 1)", "",
                   "| kernel | calls | avg ms | % |", "|---|---|---|---|"]
             for k, c, m, p in ks[:8]:
                 L.append("| %s | %d | %.3f | %.1f |" % (k[:70], c, m, p))
             L += ["", "probe_kernel / vote_kernel per-dispatch ms in launch order (warmup step, 3 timed steps, "
                   "stats pass; each step = one probe_kernel + vote_kernel pair per chunk of reads): " +
                   ", ".join("%.1f" % x for x in durs), ""]
-        L += ["## PMC (separate passes, `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, bench.py --steps 1 --warmup 0)", "",
+        L += ["## PMC (separate passes, `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, bench.py --full --steps 1 --warmup 0)", "",
               "| | bytes per launch | bytes per read |", "|---|---|---|",
               "| FETCH_SIZE | %.3e | %.1f |" % (fetch_b, fetch_b / a.reads),
               "| WRITE_SIZE | %.3e | %.1f |" % (write_b, write_b / a.reads),

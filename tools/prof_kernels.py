@@ -79,7 +79,7 @@ def main():
     ap.add_argument("--extra", type=int, default=1, help="steps after the timed ones (prof_run.py host mode: 1)")
     ap.add_argument("--reads", type=int, default=50_000_000, help="reads per step (all chunks)")
     ap.add_argument("--workload", default="c3")
-    ap.add_argument("--bench-json", help="bench.py line of the traced run (launch_ms to compare)")
+    ap.add_argument("--bench-json", help="bench.py --full line of the traced run (launch_ms to compare)")
     ap.add_argument("--cmd", default="python3 tools/prof_run.py WL STEPS host", help="the profiled command")
     a = ap.parse_args()
 
