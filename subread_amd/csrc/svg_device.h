@@ -261,6 +261,7 @@ struct PParams {
 	int nps;
 	int total_subreads, reverse_r1, reverse_r2;
 	uint64_t nb_magic;        // ceil(2^64 / nb): key / nb == umulhi64(key, nb_magic) for 32-bit keys
+	uint32_t gap_magic;       // x / gap == umulhi32(x, gap_magic) for gap >= 2 (svg_plan_gap_magic)
 	uint2 *out;               // [read][end][strand][nps] (soa = 0) or [end][strand][nps][read] (soa = 1):
 	                          // x = midpoint item, y = fwd | bwd << 16
 	int soa;
@@ -269,7 +270,7 @@ struct PParams {
 	unsigned long long *stats;
 	// 2-bit packed input (svg_packed_reads) per end, read r of the chunk at base
 	// pk_starts[e][r] or pk_base0[e] + r * pk_stride[e]; seq/off unused when packed
-	// bucket-line kernel: reads per LDS group; list of probes with > 59-item buckets
+	// bucket-line kernel: reads per LDS group (a power of two <= 64); list of probes with > 59-item buckets
 	uint32_t group;
 	uint32_t *big_list, *big_count;   // [region][big_stride] slot indexes, [region] counts
 	uint32_t big_stride, big_regions;

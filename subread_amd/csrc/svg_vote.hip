@@ -49,6 +49,7 @@
 #include "subread_vote.h"
 #include "svg_internal.h"
 #include "svg_device.h"
+#include "svg_plan.h"
 
 #define ROWS 30
 #define SPACE 24              // GENE_VOTE_SPACE: slots a row may hold
@@ -1647,38 +1648,23 @@ __device__ __forceinline__ bool try_run(uint64_t eq, int n, int &m, int &fwd, in
 	return true;
 }
 
-// 16-mer key of probe p (subread x gap slot) of strand s of end e of read r (genekey2int,
-// input-files.c:1232, at the subread offset of core.c:3117-3171); false if the read has no
-// such probe (shorter than 15 + gap, or p beyond its applied subreads)
-template <int ENDS, bool PACKED>
-__device__ __forceinline__ bool probe_key(const PParams &pp, uint32_t r, int e, int s, int p, uint32_t &key)
+// the 16-mer key (genekey2int, input-files.c:1232) of strand s of end e of a read of len kept
+// bases at read offset off; base = the read's first base in the packed words (PACKED) or its
+// offset in the text.  Strand 1 = reverse_read of strand 0, strand 0 = the input,
+// reverse-complemented for -S (R2 by default)
+template <bool PACKED>
+__device__ __forceinline__ uint32_t probe_window(const PParams &pp, int e, int s, uint64_t base, int len, int off)
 {
-	int len = e ? pp.len2[r] : pp.len1[r];
-	if (len > SVG_READ_KEEP) len = SVG_READ_KEEP;
-	const int gap = pp.ix.gap;
-	if (len < 15 + gap) return false;
-	const int cr = (len - 15 - gap) << 16;
-	int step;
-	if (len <= 160) { step = cr / (pp.total_subreads - 1); if (step < (gap << 16)) step = gap << 16; }
-	else { step = 6 << 16; if (cr / step > 62) step = cr / 62; }
-	const int np = (1 + cr / step) * gap;
-	if (p >= np) return false;
-	const int k = p / gap, x = p - k * gap;
-	int off = (int)(((int64_t)step * k) >> 16);
-	if (gap > 1) off -= off % gap - x;
-	// 16 bases of strand s at off; strand 1 = reverse_read of strand 0, strand 0 = the input,
-	// reverse-complemented for -S (R2 by default)
 	const int rev = e ? pp.reverse_r2 : pp.reverse_r1;
 	const bool direct = s == rev;
 	const int start = direct ? off : len - 16 - off;
-	key = 0;
+	uint32_t key = 0;
 	if constexpr (PACKED) {
 		// 2-bit input (svg_packed_reads): the 16 codes at base k0 are one 32-bit window,
 		// already genekey2int's key.  Reverse strand: complement (~code; an exception base
 		// complements to 'N' = 3) and reverse the 2-bit groups.  Strand 1 of a reversed
 		// read is comp(comp(input)): the codes, with exception bases turned into 'N'.
-		const uint64_t k0 = (pp.pk_starts[e] ? pp.pk_starts[e][r] : pp.pk_base0[e] + (uint64_t)r * pp.pk_stride[e]) +
-		                    (uint64_t)start;
+		const uint64_t k0 = base + (uint64_t)start;
 		const uint32_t *bw = pp.pk_bases[e] + (k0 >> 4);
 		const uint32_t s2 = 2u * (uint32_t)(k0 & 15u);
 		const uint32_t W = s2 ? (bw[0] << s2) | (bw[1] >> (32u - s2)) : bw[0];
@@ -1700,7 +1686,7 @@ __device__ __forceinline__ bool probe_key(const PParams &pp, uint32_t r, int e, 
 			key = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
 		}
 	} else {
-		const char *src = (e ? pp.seq2 : pp.seq1) + (e ? pp.off2[r] : pp.off1[r]) + start;
+		const char *src = (e ? pp.seq2 : pp.seq1) + base + start;
 		const uintptr_t a = (uintptr_t)src;
 		const uint32_t *w = (const uint32_t *)(a & ~(uintptr_t)3);
 		const int sh = (int)(a & 3);
@@ -1717,6 +1703,27 @@ __device__ __forceinline__ bool probe_key(const PParams &pp, uint32_t r, int e, 
 			key |= b2i(c) << (30 - 2 * i);
 		}
 	}
+	return key;
+}
+
+// where read r of end e starts: its first base in the packed words, or its offset in the text
+template <bool PACKED>
+__device__ __forceinline__ uint64_t probe_read_base(const PParams &pp, uint32_t r, int e)
+{
+	if constexpr (PACKED) return pp.pk_starts[e] ? pp.pk_starts[e][r] : pp.pk_base0[e] + (uint64_t)r * pp.pk_stride[e];
+	else return e ? pp.off2[r] : pp.off1[r];
+}
+
+// 16-mer key of probe p (subread x gap slot) of strand s of end e of read r, at the subread
+// offset of core.c:3117-3171 (svg_plan.h); false if the read has no such probe (shorter than
+// 15 + gap, or p beyond its applied subreads)
+template <int ENDS, bool PACKED>
+__device__ __forceinline__ bool probe_key(const PParams &pp, uint32_t r, int e, int s, int p, uint32_t &key)
+{
+	int len, step;
+	const int gap = pp.ix.gap;
+	if (p >= svg_plan_read(e ? pp.len2[r] : pp.len1[r], gap, pp.total_subreads, &len, &step)) return false;
+	key = probe_window<PACKED>(pp, e, s, probe_read_base<PACKED>(pp, r, e), len, svg_plan_off(step, p, gap, pp.gap_magic));
 	return true;
 }
 
@@ -1925,25 +1932,49 @@ __global__ void __launch_bounds__(256, BPC) probe_kernel(PParams pp)
 #define IMG_KHASH 2
 // probes per thread and pass of the code / key-hash line kernels (their loads in flight
 // together): 2 -- C3 0.976 -> 0.913 ms per launch, 469.6 Mreads/s (profiles/r04/bench_c3_probe2.json);
-// 3 measured the same (0.920 ms, 467.0, bench_c3_r4i.json) and 4 spills 46 registers at 8 waves/SIMD
+// 3 measured the same (0.920 ms, 467.0, bench_c3_r4i.json) and 4 spills 46 registers at 8 waves/SIMD.
+// With the per-read plan in LDS the packed code builds take 63 (SE) / 64 (PE) VGPRs at depth 2,
+// no spill (53 / 56 before); compiled only, depth 3 spills 7 / 9 VGPRs and depth 4 47 / 53, so
+// deeper values were not timed again.  The ASCII-input code and key-hash builds spill 16 and 6
+// VGPRs at depth 2 (none before)
+#ifndef SVG_PROBE_DEPTH
+#define SVG_PROBE_DEPTH 2   // (make variant VFLAGS=-DSVG_PROBE_DEPTH=3 for an A/B)
+#endif
 template <int ENDS, bool PACKED>
-struct ProbeDepth { static constexpr int value = 2; };
+struct ProbeDepth { static constexpr int value = SVG_PROBE_DEPTH; };
 
 // a probe's record from its bucket's 32-byte code (q: key / nb, the key_hi the code counts):
 // the equal-key run's bounds by two selects on the code's zero bits, gehash_go_X's binary search
 // replayed on them for the first-hit midpoint; count byte 255 = the big-bucket list
+// (items / hits: the bucket's item count and the run's length, for the statistics)
 __device__ __forceinline__ void code_record(const uint4 u0, const uint4 u1, uint32_t q, uint32_t key, uint2 &rec, bool &big,
-                                            unsigned long long &st_i, unsigned long long &st_h)
+                                            uint32_t &items, uint32_t &hits)
 {
 	const uint32_t c = u0.y & 255u, first = u0.x;
 	big = c == 255u;
+	items = hits = 0u;
 	if (!big && c) {
 		const uint64_t z[4] = {~(((uint64_t)u0.y << 32) | u0.x) & ~0xffffffffffull, ~(((uint64_t)u0.w << 32) | u0.z),
 		                       ~(((uint64_t)u1.y << 32) | u1.x), ~(((uint64_t)u1.w << 32) | u1.z)};
 		const int k = (int)q;
-		const int fe = k ? code_zero(z, k - 1) - 40 - (k - 1) : 0;
-		const int ee = code_zero(z, k) - 40 - k;   // items with key_hi <= k
-		st_i += c;
+		// zero k-1 once: the word holding it by the words' zero counts, one select inside that
+		// word; the run of key_hi == k is the ones that follow it, up to zero k -- read off a
+		// 64-bit window across the word boundary (a run of 64 or more takes the second select)
+		const int c0 = __popcll(z[0]), c1 = c0 + __popcll(z[1]), c2 = c1 + __popcll(z[2]);
+		const int j = k - 1;
+		const int w = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
+		const uint64_t za = w == 0 ? z[0] : w == 1 ? z[1] : w == 2 ? z[2] : z[3];
+		const uint64_t zb = w == 0 ? z[1] : w == 1 ? z[2] : w == 2 ? z[3] : 0ull;
+		int fe = 0, pl = 39;   // k = 0: the run starts at bit 40 of word 0
+		uint64_t wa = z[0], wb = z[1];
+		if (k) {
+			pl = select64(za, j - (w == 0 ? 0 : w == 1 ? c0 : w == 2 ? c1 : c2));
+			fe = 64 * w + pl - 40 - j;   // items with key_hi < k
+			wa = za; wb = zb;
+		}
+		const uint64_t win = (wa >> pl >> 1) | (wb << (63 - pl));
+		const int ee = win ? fe + __builtin_ctzll(win) : code_zero(z, k) - 40 - k;   // items with key_hi <= k
+		items = c;
 		if (ee > fe) {
 			const int le = ee - 1;
 			int lo = 0, hi = (int)c - 1, m;
@@ -1954,48 +1985,98 @@ __device__ __forceinline__ void code_record(const uint4 u0, const uint4 u1, uint
 				else break;
 			}
 			rec = make_uint2(first + (uint32_t)m, (uint32_t)(le - m + 1) | ((uint32_t)(m - fe) << 16));
-			st_h += (unsigned)(ee - fe);
+			hits = (uint32_t)(ee - fe);
 		}
 	}
 	if (big) rec = make_uint2(key, 0xffffffffu);
+}
+
+// Probe i of a read group of probe_line_kernel (1 << lg reads from r0, nr of them present),
+// slot-major: i = slot * G + read, so that a wave is one slot of 64 reads (or 64 / G slots) and a
+// record row leaves LDS and lands in the SoA output as consecutive words, with no division.  The
+// read end's plan (LDS, written once per group) is svg_plan_pack's three words: its base
+// (probe_read_base), kept length, subread step and number of probes.  Gives the probe's key; false: an idle lane of a partial
+// group, or a probe the read does not have.  A probe's place in the LDS stage (line_stage) and its
+// index in the output records (line_outidx) are two or three instructions on i: they are computed
+// where they are used, after the bucket loads, and hold no register across them.
+template <int ENDS, bool PACKED>
+__device__ __forceinline__ bool line_probe(const PParams &pp, const uint4 *splan, uint32_t i, uint32_t lg, uint32_t nr, uint32_t &key)
+{
+	uint32_t rl, slot;
+	int e, s, p;
+	svg_plan_index<ENDS>(i, lg, (uint32_t)pp.nps, &rl, &slot, &e, &s, &p);
+	if (rl >= nr) return false;
+	const uint4 pl = splan[((uint32_t)e << lg) + rl];
+	const uint32_t w[3] = {pl.x, pl.y, pl.z};
+	if (p >= svg_plan_np(w)) return false;
+	key = probe_window<PACKED>(pp, e, s, svg_plan_base(w), svg_plan_len(w), svg_plan_off(svg_plan_step(w), p, pp.ix.gap, pp.gap_magic));
+	return true;
+}
+
+// probe i's place in the LDS stage: i itself for the SoA output; for the AoS output a row is rotated
+// by its slot, which keeps the read-major copy-out off a single bank
+__device__ __forceinline__ uint32_t line_stage(const PParams &pp, uint32_t i, uint32_t lg)
+{
+	const uint32_t m = (1u << lg) - 1u;
+	return pp.soa ? i : (i & ~m) | ((i + (i >> lg)) & m);
+}
+
+// probe i's index in the output records (the big-bucket list's entry)
+template <int ENDS>
+__device__ __forceinline__ uint32_t line_outidx(const PParams &pp, uint32_t i, uint32_t lg, uint32_t r0)
+{
+	const uint32_t r = r0 + (i & ((1u << lg) - 1u)), slot = i >> lg;
+	return pp.soa ? slot * pp.n_reads + r : r * (ENDS * 2u * (uint32_t)pp.nps) + slot;
 }
 
 template <int ENDS, bool PACKED, int IMG>
 __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 {
 	__shared__ uint2 srec[PROBE_GROUP_RECS];
+	__shared__ uint4 splan[ENDS * 64];   // per read end of the group: line_probe's plan
 	__shared__ uint32_t s_big;   // entries of this block's region of the big-bucket list
 	const DevIndex &ix = pp.ix;
-	const uint32_t nps = (uint32_t)pp.nps, per_read = ENDS * 2 * nps, n = pp.n_reads, G = pp.group;
-	const uint32_t ngroups = (n + G - 1) / G, per_blk = (ngroups + gridDim.x - 1) / gridDim.x;
+	// pp.group is a power of two <= 64 (svg_plan_group_log2)
+	const uint32_t nps = (uint32_t)pp.nps, per_read = ENDS * 2 * nps, n = pp.n_reads, G = pp.group, lg = 31u - (uint32_t)__clz(G);
+	const uint32_t ngroups = (n + G - 1) >> lg, per_blk = (ngroups + gridDim.x - 1) / gridDim.x;
 	const uint32_t g_end = min(ngroups, (blockIdx.x + 1) * per_blk);
 	uint32_t *const big_list = pp.big_list + (size_t)blockIdx.x * pp.big_stride;
-	unsigned long long st_p = 0, st_i = 0, st_h = 0;
+	// statistics only when asked (block-uniform): 32-bit per-thread counts, widened at the wave reduction
+	const bool stats = pp.stats != nullptr;
+	uint32_t st_p = 0, st_i = 0, st_h = 0;
 	if (threadIdx.x == 0) s_big = 0;
 	__syncthreads();
 	// contiguous group ranges per block: neighbouring reads stay on one XCD's L2
 	for (uint32_t g = blockIdx.x * per_blk; g < g_end; g++) {
-		const uint32_t r0 = g * G, nr = min(G, n - r0), np = nr * per_read, npr = (np + 255u) & ~255u;
+		// (np counts the idle lanes of a partial last group: at most PROBE_GROUP_RECS)
+		const uint32_t r0 = g << lg, nr = min(G, n - r0), np = per_read << lg, npr = (np + 255u) & ~255u;
+		// what depends on the read alone, once per read end (the probe loops below run after the barrier)
+		if (threadIdx.x < ((uint32_t)ENDS << lg)) {
+			const uint32_t rl = threadIdx.x & (G - 1u);
+			const int e = (int)(threadIdx.x >> lg);
+			uint4 pl = make_uint4(0u, 0u, 0u, 0u);
+			if (rl < nr) {
+				const uint32_t r = r0 + rl;
+				int len, step;
+				const int nprobe = svg_plan_read(e ? pp.len2[r] : pp.len1[r], ix.gap, pp.total_subreads, &len, &step);
+				uint32_t w[3];
+				svg_plan_pack(probe_read_base<PACKED>(pp, r, e), len, step, nprobe, w);
+				pl = make_uint4(w[0], w[1], w[2], 0u);
+			}
+			splan[threadIdx.x] = pl;
+		}
+		__syncthreads();
 		// bucket code: ProbeDepth<ENDS, PACKED>::value probes per thread and pass -- their keys, then their 32-byte code loads
 		// in flight together, then their decodes (the decode's selects and search replay no longer
 		// sit between one probe's load and the next one's)
 		if constexpr (IMG == IMG_CODE) for (uint32_t i0 = threadIdx.x; i0 < npr; i0 += 256u * ProbeDepth<ENDS, PACKED>::value) {
-			uint32_t key[ProbeDepth<ENDS, PACKED>::value], outidx[ProbeDepth<ENDS, PACKED>::value], q[ProbeDepth<ENDS, PACKED>::value];
+			uint32_t key[ProbeDepth<ENDS, PACKED>::value], q[ProbeDepth<ENDS, PACKED>::value];
 			bool ok[ProbeDepth<ENDS, PACKED>::value];
 #pragma unroll
 			for (int t = 0; t < ProbeDepth<ENDS, PACKED>::value; t++) {
 				const uint32_t i = i0 + 256u * (uint32_t)t;
-				key[t] = outidx[t] = q[t] = 0u;
-				ok[t] = false;
-				if (i < np) {
-					const uint32_t rl = i / per_read, rem = i - rl * per_read, r = r0 + rl;
-					const int e = ENDS == 2 ? (int)(rem / (2 * nps)) : 0;
-					const uint32_t rem2 = rem - (uint32_t)e * 2 * nps;
-					const int s = rem2 >= nps ? 1 : 0;
-					const int p = (int)(rem2 - (uint32_t)s * nps);
-					outidx[t] = pp.soa ? rem * n + r : r * per_read + rem;
-					ok[t] = probe_key<ENDS, PACKED>(pp, r, e, s, p, key[t]);
-				}
+				key[t] = q[t] = 0u;
+				ok[t] = i < np && line_probe<ENDS, PACKED>(pp, splan, i, lg, nr, key[t]);
 			}
 			uint4 u0[ProbeDepth<ENDS, PACKED>::value], u1[ProbeDepth<ENDS, PACKED>::value];
 #pragma unroll
@@ -2015,8 +2096,9 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 				uint2 rec = make_uint2(0u, 0u);
 				bool big = false;
 				if (ok[t]) {
-					st_p++;
-					code_record(u0[t], u1[t], q[t], key[t], rec, big, st_i, st_h);
+					uint32_t items, hits;
+					code_record(u0[t], u1[t], q[t], key[t], rec, big, items, hits);
+					if (stats) { st_p++; st_i += items; st_h += hits; }
 				}
 				const unsigned long long bm = ballot(big);
 				if (bm) {
@@ -2024,32 +2106,23 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 					uint32_t base = 0;
 					if (lane_id() == leader) base = atomicAdd(&s_big, (uint32_t)__popcll(bm));
 					base = __shfl(base, leader);
-					if (big) big_list[base + lanes_below(bm)] = outidx[t];
+					if (big) big_list[base + lanes_below(bm)] = line_outidx<ENDS>(pp, i, lg, r0);
 				}
-				if (i < np) srec[i] = rec;
+				if (i < np) srec[line_stage(pp, i, lg)] = rec;
 			}
 		}
 		// key-hash image in 32-byte sectors: the same pass (the probes' first sectors in flight
 		// together; an overflow chain continues from the next sector)
 		if (IMG == IMG_KHASH && ix.khash_sec) for (uint32_t i0 = threadIdx.x; i0 < npr; i0 += 256u * ProbeDepth<ENDS, PACKED>::value) {
-			uint32_t key[ProbeDepth<ENDS, PACKED>::value], outidx[ProbeDepth<ENDS, PACKED>::value];
+			uint32_t key[ProbeDepth<ENDS, PACKED>::value];
 			uint64_t L[ProbeDepth<ENDS, PACKED>::value];
 			bool ok[ProbeDepth<ENDS, PACKED>::value];
 #pragma unroll
 			for (int t = 0; t < ProbeDepth<ENDS, PACKED>::value; t++) {
 				const uint32_t i = i0 + 256u * (uint32_t)t;
-				key[t] = outidx[t] = 0u;
+				key[t] = 0u;
 				L[t] = 0u;
-				ok[t] = false;
-				if (i < np) {
-					const uint32_t rl = i / per_read, rem = i - rl * per_read, r = r0 + rl;
-					const int e = ENDS == 2 ? (int)(rem / (2 * nps)) : 0;
-					const uint32_t rem2 = rem - (uint32_t)e * 2 * nps;
-					const int s = rem2 >= nps ? 1 : 0;
-					const int p = (int)(rem2 - (uint32_t)s * nps);
-					outidx[t] = pp.soa ? rem * n + r : r * per_read + rem;
-					ok[t] = probe_key<ENDS, PACKED>(pp, r, e, s, p, key[t]);
-				}
+				ok[t] = i < np && line_probe<ENDS, PACKED>(pp, splan, i, lg, nr, key[t]);
 			}
 			uint4 a[ProbeDepth<ENDS, PACKED>::value], b4[ProbeDepth<ENDS, PACKED>::value];
 #pragma unroll
@@ -2068,9 +2141,9 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 				if (i - threadIdx.x >= npr) break;   // block-uniform
 				uint2 rec = make_uint2(0u, 0u);
 				if (ok[t]) {
-					st_p++;
-					if (pp.stats) {
+					if (stats) {
 						const uint32_t q = (uint32_t)__umul64hi((uint64_t)key[t], pp.nb_magic), b = key[t] - q * ix.nb;
+						st_p++;
 						st_i += ix.bstart[b + 1] - ix.bstart[b];
 					}
 					if (key[t] == 0xffffffffu) khash_find(ix, key[t], rec);
@@ -2079,33 +2152,26 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 						if (!khash_sector(a[t], b4[t], key[t], rec, more) && more)
 							khash_find_from(ix, key[t], L[t] + 1 == ix.khash_lines ? 0 : L[t] + 1, rec);
 					}
-					if (pp.stats) st_h += (rec.y & 0xffffu) + (rec.y >> 16);
+					if (stats) st_h += (rec.y & 0xffffu) + (rec.y >> 16);
 				}
-				if (i < np) srec[i] = rec;   // (the key-hash image has no big-bucket list)
+				if (i < np) srec[line_stage(pp, i, lg)] = rec;   // (the key-hash image has no big-bucket list)
 			}
 		}
 		if (IMG != IMG_CODE && !(IMG == IMG_KHASH && ix.khash_sec)) for (uint32_t i = threadIdx.x; i < npr; i += 256u) {
 			uint2 rec = make_uint2(0u, 0u);
 			bool big = false;
-			uint32_t outidx = 0;
-			if (i < np) {
-				const uint32_t rl = i / per_read, rem = i - rl * per_read, r = r0 + rl;
-				const int e = ENDS == 2 ? (int)(rem / (2 * nps)) : 0;
-				const uint32_t rem2 = rem - (uint32_t)e * 2 * nps;
-				const int s = rem2 >= nps ? 1 : 0;
-				const int p = (int)(rem2 - (uint32_t)s * nps);
-				outidx = pp.soa ? rem * n + r : r * per_read + rem;
-				uint32_t key;
-				if (IMG == IMG_KHASH && probe_key<ENDS, PACKED>(pp, r, e, s, p, key)) {
+			uint32_t key = 0;
+			if (i < np && line_probe<ENDS, PACKED>(pp, splan, i, lg, nr, key)) {
+				if (IMG == IMG_KHASH) {
 					// the key's record from its 64-byte line (and the overflow chain)
-					st_p++;
-					if (pp.stats) {
+					if (stats) {
 						const uint32_t q = (uint32_t)__umul64hi((uint64_t)key, pp.nb_magic), b = key - q * ix.nb;
+						st_p++;
 						st_i += ix.bstart[b + 1] - ix.bstart[b];
 					}
 					khash_find(ix, key, rec);
-					if (pp.stats) st_h += (rec.y & 0xffffu) + (rec.y >> 16);
-				} else if (IMG == IMG_LINE && probe_key<ENDS, PACKED>(pp, r, e, s, p, key)) {
+					if (stats) st_h += (rec.y & 0xffffu) + (rec.y >> 16);
+				} else if (IMG == IMG_LINE) {
 					const uint32_t q = (uint32_t)__umul64hi((uint64_t)key, pp.nb_magic);
 					const uint32_t b = key - q * ix.nb;
 					// the bucket's 64-byte line: bounds and u8 keys in one random access
@@ -2114,7 +2180,7 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 #pragma unroll
 					for (int k = 0; k < 4; k++) lw[k] = l4[k];
 					const uint32_t c = lw[0].y & 255u, first = lw[0].x;
-					st_p++;
+					if (stats) st_p++;
 					big = c > 59u;
 					if (!big && c) {
 						// u8 keys at bytes 5..63 of the line, equal keys by a zero-byte test
@@ -2135,10 +2201,10 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 						int m = 0, fwd = 0, bwd = 0;
 						bool hit = false;
 						if (try_run(eq, (int)c, m, fwd, bwd, hit)) {
-							st_i += c;
+							if (stats) st_i += c;
 							if (hit) {
 								rec = make_uint2(first + (uint32_t)m, (uint32_t)fwd | ((uint32_t)bwd << 16));
-								st_h += (unsigned)(fwd + bwd);
+								if (stats) st_h += (uint32_t)(fwd + bwd);
 							}
 						} else big = true;   // unsorted bucket: the literal search, in probe_big_kernel
 					}
@@ -2153,28 +2219,35 @@ __global__ void __launch_bounds__(256, 8) probe_line_kernel(PParams pp)
 				uint32_t base = 0;
 				if (lane_id() == leader) base = atomicAdd(&s_big, (uint32_t)__popcll(bm));
 				base = __shfl(base, leader);
-				if (big) big_list[base + lanes_below(bm)] = outidx;
+				if (big) big_list[base + lanes_below(bm)] = line_outidx<ENDS>(pp, i, lg, r0);
 			}
-			if (i < np) srec[i] = rec;
+			if (i < np) srec[line_stage(pp, i, lg)] = rec;
 		}
 		__syncthreads();
-		for (uint32_t i = threadIdx.x; i < np; i += 256u) {
-			if (pp.soa) {
-				const uint32_t row = i / nr, rl = i - row * nr;
-				pp.out[(size_t)row * n + r0 + rl] = srec[rl * per_read + row];
-			} else pp.out[(size_t)r0 * per_read + i] = srec[i];
+		if (pp.soa) {
+			// a row of the group: consecutive LDS words to consecutive reads of the output row
+			for (uint32_t i = threadIdx.x; i < np; i += 256u) {
+				const uint32_t rl = i & (G - 1u);
+				if (rl < nr) pp.out[(size_t)(i >> lg) * n + r0 + rl] = srec[i];
+			}
+		} else {
+			// read-major records: a wave per read, its slots from the rotated rows (line_probe)
+			for (uint32_t rl = threadIdx.x >> 6; rl < nr; rl += 4u)
+				for (uint32_t slot = threadIdx.x & 63u; slot < per_read; slot += 64u)
+					pp.out[(size_t)(r0 + rl) * per_read + slot] = srec[(slot << lg) | ((rl + slot) & (G - 1u))];
 		}
 		__syncthreads();
 	}
 	if (threadIdx.x == 0) pp.big_count[blockIdx.x] = s_big;
-	if (pp.stats) {
+	if (stats) {
+		unsigned long long sp = st_p, si = st_i, sh = st_h;
 		for (int o = 32; o; o >>= 1) {
-			st_p += __shfl_xor(st_p, o); st_i += __shfl_xor(st_i, o); st_h += __shfl_xor(st_h, o);
+			sp += __shfl_xor(sp, o); si += __shfl_xor(si, o); sh += __shfl_xor(sh, o);
 		}
-		if (lane_id() == 0 && st_p) {
-			atomicAdd(&pp.stats[0], st_p);
-			atomicAdd(&pp.stats[1], st_i);
-			atomicAdd(&pp.stats[2], st_h);
+		if (lane_id() == 0 && sp) {
+			atomicAdd(&pp.stats[0], sp);
+			atomicAdd(&pp.stats[1], si);
+			atomicAdd(&pp.stats[2], sh);
 		}
 	}
 }
@@ -3422,6 +3495,10 @@ int svg_vote_prepare(svg_index *h, const svg_params *p, const svg_reads *r1, con
 	pp.nps = nps;
 	pp.total_subreads = p->total_subreads; pp.reverse_r1 = p->reverse_r1; pp.reverse_r2 = p->reverse_r2;
 	pp.nb_magic = ~0ull / h->dix.nb + 1;   // ceil(2^64 / nb), nb is not a power of two
+	// (the multiply-shift and the packed plan are exact for gap <= 192; a wider gap passes the
+	// 192-probe check above only with no probe inside the announced bound, where a single probe
+	// slot p = 0 at offset 0 remains: svg_plan.h, tests/native/plan_check.cc)
+	pp.gap_magic = svg_plan_gap_magic(h->dix.gap);
 	pp.stats = kp.stats;
 	// align mode, reads <= 160 bp: lane-per-read (SE) / lane-per-pair (PE) fast path
 	// (svg_lane.hip), probe records in SoA layout
@@ -3469,9 +3546,8 @@ int svg_vote_chunk_probe(svg_index *h, VoteJob *job, uint64_t c0, uint64_t cn, i
 #define PROBE_LAUNCH(E, L, P) hipLaunchKernelGGL((probe_kernel<E, 8, L, P>), dim3((unsigned)pb), dim3(256), 0, st, pp)
 	if (h->dix.bline || h->dix.bcode || h->dix.khash) {
 		// bucket lines: grouped probe kernel + the big-bucket kernel on its list
-		pp.group = (uint32_t)(PROBE_GROUP_RECS / job->per_read);
-		if (pp.group > 64) pp.group = 64;
-		if (pp.group < 1) pp.group = 1;
+		// a power of two: the kernel splits a probe index by mask and shift
+		pp.group = 1u << svg_plan_group_log2(PROBE_GROUP_RECS, (uint32_t)job->per_read);
 		const uint64_t ng = (cn + pp.group - 1) / pp.group;
 		// grid: 32 blocks per CU (4 rounds of the 8 resident); option probe_cap sets blocks per CU
 		const int64_t pc = svg_get_option("probe_cap");

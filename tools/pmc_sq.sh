@@ -1,6 +1,8 @@
 #!/bin/bash
 # SQ instruction/stall counters per kernel (three separate --pmc passes, no traces) of the
-# host path bench.py times (tools/prof_run.py ... host: 1 warmup + 1 step).
+# host path bench.py times.  The profiled process (tools/prof_run.py ... 1 host) runs three
+# steps -- warm-up, the timed step, one more for the HIP-event record -- and every dispatch is
+# summed, so the sums are divided by three: the figures printed are per step.
 # Usage: tools/pmc_sq.sh OUTDIR [WORKLOAD]
 set -e
 out=$1; wl=${2:-c3}
@@ -17,6 +19,10 @@ done
 python3 - "$out" <<'PY'
 import sqlite3, glob, sys, collections
 out = sys.argv[1]
+# tools/prof_run.py, host branch: step() once to warm up, `steps` timed calls (the 1 passed above),
+# one more under set_timing for the kernel record -- keep this count in step with that file
+STEPS = 1 + 1 + 1
+print("counters per step (sums over the %d steps of the profiled process / %d)" % (STEPS, STEPS))
 tot = collections.defaultdict(float)
 names = ("probe_line_kernel", "probe_big_kernel", "probe_kernel", "gather_kernel", "lane_kernel", "vote_kernel",
          "compact_records", "unpack_reads")
@@ -30,7 +36,7 @@ for d in sorted(glob.glob(out + "/p*/")):
         for k, n, v in c.execute("select kernel_name, counter_name, value from counters_collection"):
             kn = short(k)
             if kn:
-                tot[(kn, n)] += float(v)
+                tot[(kn, n)] += float(v) / STEPS
 for kn in names:
     rows = dict((n, v) for (k, n), v in tot.items() if k == kn)
     if not rows:
