@@ -1148,7 +1148,7 @@ int svg_events_add_batch(svg_events *t, const svg_genome_arrays *g, const svg_pa
 }
 
 /* ------------------------------------------------------------------ merge (finalise) */
-typedef struct { const svg_event *e; uint64_t order; } mref_t;
+typedef struct { const svg_event *e; } mref_t;
 
 /* conc_sort_compare, core-indel.c:944-970 (|value| 2-3: different events, 0-1: same event) */
 static int conc_compare(const svg_event *l, const svg_event *r)
@@ -1168,28 +1168,51 @@ static int conc_compare(const svg_event *l, const svg_event *r)
 	return 0;
 }
 
-static int mref_cmp(const void *a, const void *b)
+/* merge_sort, core.c:4716-4753, with conc_sort_merge (core-indel.c:973-988): runs of up to 11
+ * records are selection-sorted by exchanges, which is not stable, so which of two equal records
+ * of one event comes last -- and gives the merged body its critical_read_id and increasing-
+ * coordinate flags -- depends on this exact order */
+static void mref_sort(mref_t *a, uint64_t start, uint64_t items, mref_t *tmp)
 {
-	const mref_t *x = a, *y = b;
-	int c = conc_compare(x->e, y->e);
-	if (c) return c;
-	return x->order < y->order ? -1 : x->order > y->order;
+	if (items > 11) {
+		const uint64_t half = items / 2, end1 = start + half, end2 = start + items;
+		uint64_t p1 = start, p2 = end1, w;
+		mref_sort(a, start, half, tmp);
+		mref_sort(a, end1, items - half, tmp);
+		for (w = 0; w < items; w++) {
+			if (p1 >= end1 || (p2 < end2 && conc_compare(a[p1].e, a[p2].e) > 0)) tmp[w] = a[p2++];
+			else tmp[w] = a[p1++];
+		}
+		memcpy(a + start, tmp, sizeof(mref_t) * items);
+	} else {
+		uint64_t i, j;
+		for (i = start; i + 1 < start + items; i++) {
+			uint64_t min_j = i;
+			for (j = i + 1; j < start + items; j++)
+				if (conc_compare(a[min_j].e, a[j].e) > 0) min_j = j;
+			if (i != min_j) { mref_t x = a[i]; a[i] = a[min_j]; a[min_j] = x; }
+		}
+	}
 }
 
 int svg_events_merge(svg_events *dst, svg_events *const *tables, int n)
 {
 	uint64_t total = 0, i, k = 0, start;
-	mref_t *refs;
+	mref_t *refs, *tmp;
 	int ti;
 	if (!dst || (n > 0 && !tables)) { svg_set_error("svg_events_merge: NULL argument"); return SVG_E_ARG; }
 	for (ti = 0; ti < n; ti++)
 		if (!tables[ti] || tables[ti] == dst) { svg_set_error("svg_events_merge: NULL table or dst among the inputs"); return SVG_E_ARG; }
 	for (ti = 0; ti < n; ti++) total += tables[ti]->n;
 	refs = malloc(sizeof(mref_t) * (total + 1));
+	if (!refs) { svg_set_error("out of memory"); return SVG_E_NOMEM; }
 	for (ti = 0; ti < n; ti++)
 		for (i = 0; i < tables[ti]->n; i++)
-			if (tables[ti]->ev[i].event_type) { refs[k].e = &tables[ti]->ev[i]; refs[k].order = k; k++; }
-	qsort(refs, k, sizeof(mref_t), mref_cmp);
+			if (tables[ti]->ev[i].event_type) { refs[k].e = &tables[ti]->ev[i]; k++; }
+	tmp = malloc(sizeof(mref_t) * (k + 1));
+	if (!tmp) { free(refs); svg_set_error("out of memory"); return SVG_E_NOMEM; }
+	mref_sort(refs, 0, k, tmp);
+	free(tmp);
 	/* a group of records of one event: the merged body is a copy of the group's last record
 	 * plus the sums / maxima of the others (core-indel.c:1058-1111) */
 	for (start = 0; start < k;) {

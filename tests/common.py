@@ -68,7 +68,282 @@ def lrrow54_genome():
     return Genome(g.names, [a, g.seqs[1]])
 
 
-CUSTOM_GENOMES = {"lrrow54": lrrow54_genome}
+# ---- vtedge: a genome built to reach the edges of the short-read vote table (gene_vote_t: 30 rows
+# of 24 slots, row (kv / 5) % 30; sorted-hashtable.c:937-1123) and of the lane kernels' limits.
+# Constructs, each with its own random unit, a VTEDGE_GAP of i.i.d. sequence apart:
+#   t150_<n>   tandem array of n copies of a 150-bp unit (150 = 5 * 30: every copy in one row)
+#   r155_<n>   unit 155: each copy one row further, copies further apart than any tolerance
+#   r145_40    unit 145: one row back per copy
+#   ms_<p>     microsatellite of period p, every 16-mer vtedge_ms_copies(p) times
+#   thr_<n>    unit 157, n = 99 / 100 / 101 copies: both sides of the builder's repeat threshold
+#   edge_first / edge_last   150-bp-unit arrays flush against the first contig's start and the
+#              last contig's end
+VTEDGE_CONTIGS = [160000, 120000, 100000]
+VTEDGE_SEED = 2424
+VTEDGE_GAP = 2000
+VTEDGE_T150 = (23, 24, 25, 26, 40)
+VTEDGE_R155 = (15, 16, 17, 19, 20, 21, 63, 64, 65, 80)
+VTEDGE_LADDER = (15, 16, 17, 19, 20, 21)
+VTEDGE_MS = (2, 3, 5, 6, 7, 11, 16, 17)
+VTEDGE_THR = (99, 100, 101)
+VTEDGE_EDGE_COPIES = 30
+VTEDGE_BLOCK0_OVER = 1226   # bases of chr2 in the first block of the -F -M 1 index (blocks 0..164840, 163614..)
+_COMP = np.full(256, ord("N"), np.uint8)
+for _a, _b in (("A", "T"), ("C", "G"), ("G", "C"), ("T", "A")):
+    _COMP[ord(_a)] = ord(_b)
+_ACGT = np.frombuffer(b"ACGT", np.uint8)
+
+
+def vtedge_ms_copies(p):
+    """occurrences of every 16-mer of the period-p microsatellite (its length is p * copies + 15)"""
+    return 90 if p <= 5 else 60
+
+
+def revcomp_bytes(a):
+    return _COMP[np.asarray(a, np.uint8)[::-1]]
+
+
+_vtedge_cache = []
+
+
+def vtedge_layout():
+    """-> (Genome, constructs): constructs maps a name to dict(contig, start (in the contig), flat
+    (start in the concatenated genome), unit, copies, length)."""
+    if _vtedge_cache:
+        return _vtedge_cache[0]
+    from subread_amd.sim import Genome, random_genome
+    g = random_genome(VTEDGE_CONTIGS, VTEDGE_SEED)
+    seqs = [s.copy() for s in g.seqs]
+    rng = np.random.default_rng(VTEDGE_SEED)
+    todo = [("edge_first", 150, VTEDGE_EDGE_COPIES)]
+    todo += [("t150_%d" % n, 150, n) for n in VTEDGE_T150]
+    todo += [("r155_%d" % n, 155, n) for n in VTEDGE_R155]
+    todo += [("r145_40", 145, 40)]
+    todo += [("ms_%d" % p, p, 0) for p in VTEDGE_MS]
+    todo += [("thr_%d" % n, 157, n) for n in VTEDGE_THR]
+    cons = {}
+    ctg, cur = 0, 0
+    for name, ulen, copies in todo:
+        while True:
+            unit = _ACGT[rng.integers(0, 4, ulen)]
+            # a microsatellite unit must not itself be a repeat of a shorter one
+            if not any(ulen % d == 0 and (unit == np.tile(unit[:d], ulen // d)).all() for d in range(1, ulen)):
+                break
+        if copies:
+            body = np.tile(unit, copies)
+        else:
+            body = np.tile(unit, vtedge_ms_copies(ulen) + 16 // ulen + 2)[:ulen * vtedge_ms_copies(ulen) + 15]
+        reserve = VTEDGE_GAP + (150 * VTEDGE_EDGE_COPIES if ctg == len(seqs) - 1 else 0)
+        if cur + len(body) + reserve > len(seqs[ctg]):
+            ctg, cur = ctg + 1, VTEDGE_GAP
+        assert cur + len(body) + reserve <= len(seqs[ctg]), name
+        seqs[ctg][cur:cur + len(body)] = body
+        cons[name] = dict(contig=ctg, start=cur, unit=ulen, copies=copies, length=len(body))
+        cur += len(body) + VTEDGE_GAP
+    unit = _ACGT[rng.integers(0, 4, 150)]
+    last = len(seqs) - 1
+    body = np.tile(unit, VTEDGE_EDGE_COPIES)
+    seqs[last][len(seqs[last]) - len(body):] = body
+    cons["edge_last"] = dict(contig=last, start=len(seqs[last]) - len(body), unit=150, copies=VTEDGE_EDGE_COPIES,
+                             length=len(body))
+    g = Genome(g.names, seqs)
+    for c in cons.values():
+        c["flat"] = int(g.starts[c["contig"]]) + c["start"]
+    _vtedge_cache.append((g, cons))
+    return _vtedge_cache[0]
+
+
+def vtedge_genome():
+    return vtedge_layout()[0]
+
+
+def _vt_mutate(rng, seg, L):
+    """1% substitutions and one 1-4 bp indel; seg holds L + 8 bases"""
+    r = bytearray(np.asarray(seg, np.uint8).tobytes())
+    at = int(rng.integers(8, L - 8)) if L > 20 else int(rng.integers(1, L - 1))
+    k = int(rng.integers(1, 5))
+    if rng.random() < 0.5:
+        r[at:at] = _ACGT[rng.integers(0, 4, k)].tobytes()
+    else:
+        del r[at:at + k]
+    r = np.frombuffer(bytes(r[:L]), np.uint8).copy()
+    hit = rng.random(L) < 0.01
+    r[hit] = _ACGT[rng.integers(0, 4, int(hit.sum()))]
+    return r
+
+
+class VtReads:
+    """reads of the vtedge classes: r1, r2 (ReadBatch / None), cls (class tag per read), exact
+    (no substitution or indel), strand (1: the read is the reverse complement of its source)"""
+
+    def __init__(self, s1, s2, cls, exact, strand):
+        self.r1 = ReadBatch.from_list([bytes(x) for x in s1])
+        self.r2 = ReadBatch.from_list([bytes(x) for x in s2]) if s2 is not None else None
+        self.cls = np.array(cls)
+        self.exact = np.array(exact, bool)
+        self.strand = np.array(strand, np.uint8)
+
+    def select(self, keep):
+        idx = np.flatnonzero(keep)
+        return VtReads([self.r1.read(int(i)) for i in idx],
+                       [self.r2.read(int(i)) for i in idx] if self.r2 is not None else None,
+                       self.cls[idx], self.exact[idx], self.strand[idx])
+
+
+def _vt_finish(rng, rows, paired):
+    order = rng.permutation(len(rows))
+    rows = [rows[i] for i in order]
+    return VtReads([r[0].tobytes() for r in rows], [r[1].tobytes() for r in rows] if paired else None,
+                   [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows])
+
+
+def vtedge_se_reads(per, seed, with_161=False, ladder=(16, 17, 18, 19), block_bounds=False):
+    """`per` reads of every single-end class, in a seeded random order.
+      <array>        100- and 150-bp reads inside each array / microsatellite: half exact, half
+                     with 1% substitutions and one 1-4 bp indel, both strands
+      lad<L>_<n>     exact L = 16..19 bp reads inside one unit of the r155_<n> array (every 16-mer of
+                     the read n times in the genome): at gap 1 a read has L - 15 subreads, so
+                     (L - 15) * n candidates and n slots on its own strand.  A gapped index takes
+                     ladder=(18, 19, 20, 21): there the reference reads past the end of a read
+                     shorter than 18 bases, which is outside what this project reproduces
+      l160_<array>   160-bp (with_161: 160- and 161-bp) reads in the 40-copy arrays
+      bnd_first / bnd_last   20 random bases + the first 80 of the first contig / the last 80 of
+                     the last contig + 20 random bases
+    block_bounds adds the classes for a multi-block index (-F -M 1 puts the second block's first
+    base at chr2's first base; its low border is that position rounded down to a multiple of 4,
+    2 bases before it; the first block runs VTEDGE_BLOCK0_OVER bases into chr2):
+      cs<k>_<p>      p random bases + the first 100 - p of contig k (k = 2, 3; p = 2, 3, 20): the
+                     subreads past the prefix vote for p bases before the contig, on the low
+                     border (p = 2) and below it (p = 3, 20) where a block starts there
+      ce<k>_<p>      the mirror image at the end of contig k (k = 1, 2)
+      blkhigh        exact 100-bp reads of chr2 starting VTEDGE_BLOCK0_OVER - 100 +- 25 bases in:
+                     at and past the first block's high border (block end - read length)"""
+    g, cons = vtedge_layout()
+    rng = np.random.default_rng(seed)
+    f = g.flat
+    rows = []
+
+    def emit(src, cls, exact):
+        st = int(rng.random() < 0.5)
+        rows.append((revcomp_bytes(src) if st else np.asarray(src, np.uint8), None, cls, exact, st))
+
+    def inside(c, cls, lengths, i):
+        L = int(lengths[i % len(lengths)])
+        s = c["flat"] + int(rng.integers(0, c["length"] - L - 8))
+        if (i // len(lengths)) % 2 == 0:
+            emit(f[s:s + L], cls, True)
+        else:
+            emit(_vt_mutate(rng, f[s:s + L + 8], L), cls, False)
+
+    for name, c in cons.items():
+        for i in range(per):
+            inside(c, name, (100, 150), i)
+    for n in VTEDGE_LADDER:
+        c = cons["r155_%d" % n]
+        for L in ladder:
+            for i in range(per):
+                s = c["flat"] + 155 * int(rng.integers(0, n)) + int(rng.integers(0, 155 - L + 1))
+                emit(f[s:s + L], "lad%d_%d" % (L, n), True)
+    for name in ("t150_40", "r155_80", "r145_40"):
+        for i in range(per):
+            inside(cons[name], "l160_" + name, (160, 161) if with_161 else (160,), i)
+    first, last = g.seqs[0], g.seqs[-1]
+    for i in range(per):
+        emit(np.concatenate([_ACGT[rng.integers(0, 4, 20)], first[:80]]), "bnd_first", False)
+        emit(np.concatenate([last[-80:], _ACGT[rng.integers(0, 4, 20)]]), "bnd_last", False)
+    if block_bounds:
+        for p in (2, 3, 20):
+            for i in range(per):
+                for k in (1, 2):
+                    emit(np.concatenate([_ACGT[rng.integers(0, 4, p)], g.seqs[k][:100 - p]]), "cs%d_%d" % (k + 1, p), False)
+                    emit(np.concatenate([g.seqs[k - 1][p - 100:], _ACGT[rng.integers(0, 4, p)]]), "ce%d_%d" % (k, p), False)
+        for i in range(per):
+            s = VTEDGE_BLOCK0_OVER - 100 + int(rng.integers(-25, 26))
+            emit(g.seqs[1][s:s + 100], "blkhigh", True)
+    return _vt_finish(rng, rows, False)
+
+
+def vtedge_pe_reads(per, seed):
+    """`per` pairs of every paired class (R2 the reverse complement of its source, -S fr):
+      pe_r155_<n>_fl   R1 100 bp inside one unit of the r155_<n> array (n = 63, 64, 65, 80: n
+                       distinct end-0 positions), R2 in the unique flank 200-400 bp past the array
+      pe_fl_r155_<n>   the other way round: R1 in the flank before the array, R2 inside it
+      pe_t150_<n>      both ends in the same t150 array"""
+    g, cons = vtedge_layout()
+    rng = np.random.default_rng(seed)
+    f = g.flat
+    rows = []
+
+    def emit(a, b, cls):
+        a, b = np.asarray(a, np.uint8), revcomp_bytes(b)
+        st = int(rng.random() < 0.5)
+        rows.append(((b, a) if st else (a, b)) + (cls, True, st))
+
+    for n in (63, 64, 65, 80):
+        c = cons["r155_%d" % n]
+        end = c["flat"] + c["length"]
+        for i in range(per):
+            s = c["flat"] + 155 * int(rng.integers(n - 3, n)) + int(rng.integers(0, 56))
+            d = end + int(rng.integers(200, 401))
+            rows.append((np.asarray(f[s:s + 100], np.uint8), revcomp_bytes(f[d:d + 100]), "pe_r155_%d_fl" % n, True, 0))
+            s = c["flat"] + 155 * int(rng.integers(0, 3)) + int(rng.integers(0, 56))
+            d = c["flat"] - int(rng.integers(200, 401)) - 100
+            rows.append((np.asarray(f[d:d + 100], np.uint8), revcomp_bytes(f[s:s + 100]), "pe_fl_r155_%d" % n, True, 0))
+    for n in (24, 25, 40):
+        c = cons["t150_%d" % n]
+        for i in range(per):
+            L = int(rng.choice([100, 150]))
+            ins = int(rng.integers(L, 600))
+            s = c["flat"] + int(rng.integers(0, c["length"] - ins))
+            emit(f[s:s + L], f[s + ins - L:s + ins], "pe_t150_%d" % n)
+    return _vt_finish(rng, rows, True)
+
+
+VTEDGE_SJ_ARRAYS = ("t150_25", "t150_40", "r155_20", "r155_65") + tuple("ms_%d" % p for p in VTEDGE_MS)
+
+
+def vtedge_sj_reads(per, seed, lengths=(100, 200)):
+    """`per` spliced reads per class sj<L>_<array>, simulate_spliced_reads-style: the first exon
+    part ends inside the array right before a GT, the second starts in unique sequence right after
+    an AG 60..20000 bases further on the same contig; 0.5% substitutions, both strands.  (A
+    microsatellite whose unit holds no GT has no class.)"""
+    g, cons = vtedge_layout()
+    rng = np.random.default_rng(seed)
+    f = g.flat
+    ag_end = np.flatnonzero((f[:-1] == ord("A")) & (f[1:] == ord("G"))).astype(np.int64) + 2
+    spans = sorted((c["flat"], c["flat"] + c["length"]) for c in cons.values())
+    rows = []
+    for L in lengths:
+        for name in VTEDGE_SJ_ARRAYS:
+            c = cons[name]
+            seg = f[c["flat"]:c["flat"] + c["length"]]
+            gt = c["flat"] + np.flatnonzero((seg[:-1] == ord("G")) & (seg[1:] == ord("T")))
+            if not len(gt):
+                continue
+            cend = int(g.starts[c["contig"]]) + int(g.lens[c["contig"]])
+            got = 0
+            while got < per:
+                a = int(rng.integers(20, L - 19))
+                x = int(gt[rng.integers(0, len(gt))])
+                if x - a < c["flat"]:
+                    continue
+                d = int(np.exp(rng.uniform(np.log(60), np.log(20000))))
+                k = int(np.searchsorted(ag_end, x + d))
+                if k >= len(ag_end):
+                    continue
+                y = int(ag_end[k])
+                if y + (L - a) > cend or any(s0 < y + (L - a) and y < e0 for s0, e0 in spans):
+                    continue
+                r = np.concatenate([f[x - a:x], f[y:y + L - a]])
+                hit = rng.random(L) < 0.005
+                r[hit] = _ACGT[rng.integers(0, 4, int(hit.sum()))]
+                st = int(rng.random() < 0.5)
+                rows.append((revcomp_bytes(r) if st else r, None, "sj%d_%s" % (L, name), not hit.any(), st))
+                got += 1
+    return _vt_finish(rng, rows, False)
+
+
+CUSTOM_GENOMES = {"lrrow54": lrrow54_genome, "vtedge": vtedge_genome}
 
 
 def synth_genome(gname):
@@ -81,7 +356,8 @@ def synth_genome(gname):
 
 def index_recipe(key):
     """'<genome>_<mode>' -> (genome, gap, memory_mb, force_one_block).  full = -F -B -M 100,
-    gapped = the defaults (-M 8000), fullM<n> / gappedM<n> = -F -M <n> / -M <n> (multi-block)."""
+    gapped = the defaults (-M 8000), fullM<n> / gappedM<n> = -F -M <n> / -M <n> (multi-block).
+    The genome is chr901, one of SYNTH_GENOMES or one of CUSTOM_GENOMES (vtedge_full, vtedge_gapped)."""
     gname, mode = key.rsplit("_", 1)
     if mode == "full":
         return gname, 1, 100, True

@@ -155,7 +155,7 @@ def mixed_reads(genome, n, seed, lengths, gapped):
     return ReadBatch.from_list(out)
 
 
-def save_case(name, prog, paired, index, params_over, r1, r2, raw, ends, note):
+def save_case(name, prog, paired, index, params_over, r1, r2, raw, ends, note, extra=None):
     p = default_params(prog, paired, **params_over)
     n = len(r1)
     mb = p.multi_best
@@ -168,6 +168,8 @@ def save_case(name, prog, paired, index, params_over, r1, r2, raw, ends, note):
                 params=np.array([getattr(p, f) for f, _ in p._fields_], dtype=np.int32))
     if r2 is not None:
         arrs.update(r2_seq=r2.seq, r2_off=r2.offsets, r2_len=r2.lens)
+    if extra:
+        arrs.update(extra)
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), **arrs)
     meta = dict(program=prog, paired=paired, index=index, params_over=params_over, n=n, note=note)
     with open(os.path.join(GOLD, name + ".json"), "w") as f:
@@ -178,7 +180,83 @@ def save_case(name, prog, paired, index, params_over, r1, r2, raw, ends, note):
 from subread_amd.sim import simulate_spliced_reads  # noqa: E402
 
 
+def vtedge_cases():
+    """The vote-table edge cases on the crafted genome (tests/common.py, vtedge_*): 30 reads per
+    class.  The 161-bp reads are in the -I 16 case only: one read over 160 bp takes a whole batch
+    off the lane kernels, which the other two single-end cases are there to test."""
+    from tests.common import vtedge_se_reads, vtedge_pe_reads, vtedge_sj_reads
+    se, se161 = vtedge_se_reads(30, 101), vtedge_se_reads(30, 102, with_161=True)
+    seg = vtedge_se_reads(30, 108, ladder=(18, 19, 20, 21))
+    pe, pe2 = vtedge_pe_reads(100, 103), vtedge_pe_reads(100, 104)
+    sj, sj1, sj2 = vtedge_sj_reads(40, 105), vtedge_sj_reads(40, 106), vtedge_sj_reads(40, 107)
+    # 160 / 161-bp reads alone, at the default tolerance, on both index kinds
+    s161 = vtedge_se_reads(30, 110, with_161=True)
+    s161 = s161.select(np.char.startswith(s161.cls, "l160_"))
+    # every single-end class plus the block-border classes, for the 2-block -F -M 1 index
+    semb = vtedge_se_reads(30, 109, block_bounds=True)
+    note = "vtedge genome, %s (tests/common.py), class tags in the .npz (cls, exact, strand)"
+    return [("se_full_vtedge", PROGRAM_ALIGN, False, "vtedge_full", {}, se, None, note % "vtedge_se_reads(30, 101)"),
+            ("se_gapped_vtedge", PROGRAM_ALIGN, False, "vtedge_gapped", {}, seg, None,
+             note % "vtedge_se_reads(30, 108, ladder=(18, 19, 20, 21))"),
+            ("se_full_vtedge_I16", PROGRAM_ALIGN, False, "vtedge_full", {"max_indel_length": 16}, se161, None,
+             note % "vtedge_se_reads(30, 102, with_161=True), -I 16"),
+            ("pe_full_vtedge", PROGRAM_ALIGN, True, "vtedge_full", {}, pe, None, note % "vtedge_pe_reads(100, 103)"),
+            ("pe_gapped_vtedge", PROGRAM_ALIGN, True, "vtedge_gapped", {}, pe2, None, note % "vtedge_pe_reads(100, 104)"),
+            ("sj_se_full_vtedge", PROGRAM_SUBJUNC, False, "vtedge_full", {}, sj, None, note % "vtedge_sj_reads(40, 105)"),
+            ("sj_pe_gapped_vtedge", PROGRAM_SUBJUNC, True, "vtedge_gapped", {}, sj1, sj2,
+             note % "vtedge_sj_reads(40, 106) with vtedge_sj_reads(40, 107) as R2"),
+            ("se_full_vtedge_161", PROGRAM_ALIGN, False, "vtedge_full", {}, s161, None,
+             note % "the l160_* classes of vtedge_se_reads(30, 110, with_161=True)"),
+            ("se_gapped_vtedge_161", PROGRAM_ALIGN, False, "vtedge_gapped", {}, s161, None,
+             note % "the l160_* classes of vtedge_se_reads(30, 110, with_161=True)"),
+            ("se_mb_vtedge_fullM1", PROGRAM_ALIGN, False, "vtedge_fullM1", {}, semb, None,
+             note % "vtedge_se_reads(30, 109, block_bounds=True) on the 2-block -F -M 1 index")]
+
+
+def add_main(only):
+    """--add [case ...]: write the cases that are not committed yet (or the named ones) and add
+    their indexes' md5 to index_md5.json; no other fixture is opened for writing."""
+    tmp = tempfile.mkdtemp(prefix="svg_gold_")
+    try:
+        cases = [c for c in vtedge_cases()
+                 if (c[0] in only if only else not os.path.exists(os.path.join(GOLD, c[0] + ".npz")))]
+        with open(os.path.join(GOLD, "index_md5.json")) as f:
+            doc = json.load(f)
+        idx = {}
+        for key in sorted(set(c[3] for c in cases)):
+            gname = key.rsplit("_", 1)[0]
+            fa = os.path.join(tmp, gname + ".fa")
+            if not os.path.exists(fa):
+                synth_genome(gname).write_fasta(fa)
+            idx[key] = os.path.join(tmp, key)
+            got = build_ref_index(fa, idx[key], key)
+            assert doc["md5"].get(key, got) == got, "index %s changed" % key
+            doc["md5"][key] = got
+            doc["recipes"].setdefault(gname, "tests.common.CUSTOM_GENOMES[%r]()" % gname)
+        with open(os.path.join(GOLD, "index_md5.json"), "w") as f:
+            json.dump(doc, f, indent=1)
+        for name, prog, paired, ikey, over, a, b, note in cases:
+            r1, r2 = a.r1, (b.r1 if b is not None else a.r2)
+            extra = ["-I", str(over["max_indel_length"])] if "max_indel_length" in over else []
+            f1 = os.path.join(tmp, name + "_1.fq")
+            write_fastq(f1, r1)
+            f2 = None
+            if r2 is not None:
+                f2 = os.path.join(tmp, name + "_2.fq")
+                write_fastq(f2, r2)
+            raw = run_ref(prog, idx[ikey], f1, f2, os.path.join(tmp, name + ".bin"), extra)
+            tags = dict(cls=a.cls, exact=a.exact, strand=a.strand)
+            if b is not None:
+                tags.update(cls2=b.cls, exact2=b.exact, strand2=b.strand)
+            save_case(name, prog, paired, ikey, over, r1, r2, raw, 2 if paired else 1, note, tags)
+            save_events(name, prog, idx[ikey], r1, r2, over, tmp)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
+    if "--add" in sys.argv:
+        return add_main(set(a for a in sys.argv[1:] if not a.startswith("--")))
     tmp = tempfile.mkdtemp(prefix="svg_gold_")
     try:
         # ---- genomes and indexes

@@ -8,7 +8,7 @@ built with oracle/ref_dump_hook.c, whose SVG_REF_EVENTS_RN dump follows remove_n
 For every case of tests/golden/events/ it runs the reference on the case's reads and index
 exactly as make_golden.py's save_events does (-T 1, the same FASTQ), checks that the event
 table it dumps before remove_neighbour is the committed one byte for byte (same inputs), and
-stores the types after it.  Fixture = data (one byte per event); no reference source is stored.
+stores the types after it.  With --add it writes only the cases that have no file yet.  Fixture = data (one byte per event); no reference source is stored.
 """
 import os
 import shutil
@@ -59,11 +59,15 @@ def synthetic(tmp, cache):
 
 
 def main():
+    # --add: only the cases of tests/golden/events/ that have no events_rn file yet
+    add_only = "--add" in sys.argv
     tmp = tempfile.mkdtemp(prefix="svg_rn_")
     cache = IndexCache(tmp)
     os.makedirs(os.path.join(GOLD, "events_rn"), exist_ok=True)
     try:
         for name in EVENT_CASES:
+            if add_only and os.path.exists(os.path.join(GOLD, "events_rn", name + ".npz")):
+                continue
             c = Case(name)
             over = c.meta["params_over"]
             extra = []
@@ -91,7 +95,8 @@ def main():
             types = np.frombuffer(b[8:], np.uint8).copy()
             np.savez_compressed(os.path.join(GOLD, "events_rn", name + ".npz"), types=types)
             print("events_rn", name, n, "events,", int((types == 0).sum()), "removed")
-        synthetic(tmp, cache)
+        if not add_only:
+            synthetic(tmp, cache)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
