@@ -378,7 +378,9 @@ int  svg_cpulist_parse(const char *list, uint8_t *mask, int max);
  *   chunk, overlap              reads per probe-record chunk; 1/0 force the two-stream chunk pipeline
  *   lane                        1 lane kernels + deferral (default), 2 defer every read to the
  *                               wave kernel, 3 no lane kernels (wave kernel only)
- *   lane_unfused, lane_bin      separate gather kernel; 2 = no count bins
+ *   lane_unfused                separate gather kernel
+ *   lane_bins                   count bins of the fused lane path: 0 lists by heavier strand and
+ *                               its count (default), 1 by the larger strand count alone
  *   lane_cap, lane_pe_cap, lane_pairs, lane_mid   lane-path capacities (candidates, pairs)
  *   no_bcode, no_khash, khash64, no_bline, no_compact, kinline, khash_probe, probe_v1,
  *   no_window, probe_colmajor   probe images / probe kernel variants picked at index load

@@ -155,17 +155,30 @@ struct LParams {
 	int max_pairs;                // a pair's simples products past this go to the wave kernel (per-lane pair loop bound)
 	unsigned long long *stats;    // [3] += results; [4] += deferred reads (final pass only);
 	int stat_base, final_pass;    // diagnostics at stats[stat_base..+4]: deferrals by reason (3), candidates, deferrals
-	// count bins (fused SE path): lane_bin_kernel lists the chunk's reads by their larger strand's
-	// candidate count, bin b at bins[b * n], bin_count[b] reads; the lane kernel takes 64-read
-	// groups from the heaviest bin down (NULL: lane column k = read k or idx[k])
+	// count bins (fused SE path): lane_bin_kernel lists the chunk's reads by their heavier strand
+	// and its candidate count, list l = 2 * class + strand, bin_count[l] reads; the two lists of a
+	// class share bins[class * n .. + n): strand 0's grows up from its start, strand 1's down from
+	// its end.  The lane kernel takes 64-read groups from the heaviest class down (NULL: lane
+	// column k = read k or idx[k]).  bin_rule 1 (option lane_bins 1): one list per class, by the
+	// larger strand count alone
 	uint32_t *bins, *bin_count;
+	int bin_rule;
 };
 
-// candidate-count bins: a wave's vote loop runs as many iterations as its heaviest lane has
-// candidates, so lanes of one group should carry similar counts (C3: 19 candidates per read on
-// average, but the heaviest of 64 consecutive reads typically 30-40)
-#define LBINS 4
+// candidate-count bins: a wave's vote loop runs, per strand, as many iterations as its heaviest
+// lane has candidates on that strand, so lanes of one group should carry similar counts on the
+// same strands (C3: 19 candidates per read on average, most of them on the strand the read comes
+// from; the heaviest of 64 consecutive reads typically 30-40 on either strand)
+#define LBINS 4                // classes of the heavier strand's count
+#define LLISTS (2 * LBINS)     // x which strand is the heavier one
+#ifndef LLIGHT
+// classes of the lighter strand's count, the order inside a tile's part of a list.  1: no order
+// (read order).  16 (llight_of) cuts the vote-loop steps further but spreads a group's probe record
+// loads over its whole tile: C3 86.5 ms/step against 84.8 unordered and 86.8 before
+#define LLIGHT 1
+#endif
 __host__ __device__ constexpr int lbin_of(int c) { return c <= 8 ? 0 : (c <= 16 ? 1 : (c <= 24 ? 2 : 3)); }
+__host__ __device__ constexpr int llight_of(int c) { return LLIGHT == 1 ? 0 : c < 12 ? c : (c < 24 ? 12 + ((c - 12) >> 2) : 15); }
 
 // meta: votes [0,5) | last [5,10) | toli [10,15) | cursor [15,21) (6-bit signed) | next [21,27) |
 // end [27] | spilled [28] | x [29,31).  votes and last (a subread number + 1) are <= 31 on this
@@ -573,28 +586,35 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SVG_LAN
 	const int cutoff = lp.cutoff;
 	unsigned long long nres = 0, ndef = 0, nwhy1 = 0, nwhy2 = 0, nwhy3 = 0, ncand = 0;
 	const uint32_t m = lp.idx ? *lp.idx_count : lp.n;
-	uint32_t bc[LBINS] = {0u, 0u, 0u, 0u}, ngroups = (m + 63u) / 64u;
+	// statistics only: vote-loop steps and tail steps (the wave's largest slot count) of this wave,
+	// summed over its groups and both strands (wave-uniform)
+	uint32_t nvstep = 0, ntstep = 0;
+	uint32_t bc[LLISTS], ngroups = (m + 63u) / 64u;
+#pragma unroll
+	for (int b = 0; b < LLISTS; b++) bc[b] = 0u;
 	if (lp.bins) {
 		ngroups = 0;
 #pragma unroll
-		for (int b = 0; b < LBINS; b++) { bc[b] = lp.bin_count[b]; ngroups += (bc[b] + 63u) / 64u; }
+		for (int b = 0; b < LLISTS; b++) { bc[b] = lp.bin_count[b]; ngroups += (bc[b] + 63u) / 64u; }
 	}
 	for (uint32_t g = gw; g < ngroups; g += nw) {
 		uint32_t k, r;
 		bool live;
 		if (lp.bins) {
-			// group g of the bins, heaviest bin first (the long groups start early)
-			uint32_t gg = g;
-			int b = LBINS - 1;
-			for (; b > 0; b--) {
-				const int bb = b;
-				const uint32_t gb = (bc[bb] + 63u) / 64u;
-				if (gg < gb) break;
-				gg -= gb;
+			// group g of the lists, heaviest class first (the long groups start early), strand 1's
+			// list of a class before strand 0's
+			uint32_t gg = g, cnt = 0;
+			int b = 0;
+			bool found = false;
+#pragma unroll
+			for (int l = LLISTS - 1; l >= 0; l--) {
+				const uint32_t gb = (bc[l] + 63u) / 64u;
+				if (!found && gg < gb) { found = true; b = l; cnt = bc[l]; }
+				if (!found) gg -= gb;
 			}
 			k = gg * 64u + (uint32_t)L.lane;
-			live = k < bc[b];
-			r = live ? lp.bins[(size_t)b * lp.n + k] : 0u;
+			live = k < cnt;
+			r = live ? lp.bins[(size_t)(b >> 1) * lp.n + ((b & 1) ? lp.n - 1u - k : k)] : 0u;
 		} else {
 			k = g * 64u + (uint32_t)L.lane;
 			live = k < m;
@@ -649,6 +669,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SVG_LAN
 				if (j + 2 < mycnt) { kv_b = cb[(size_t)(j + 2) * lp.cs]; pk_b = pb[(size_t)(j + 2) * lp.cs]; }
 				if (j < mycnt && !L.dfr) L.template vote<0>(st, kv, (int)(pk & 63u), (int)(pk >> 6), high_b, lp.gap);
 			}
+			if (lp.stats) nvstep += (uint32_t)__builtin_amdgcn_readfirstlane(mc);
 			} else {
 			// ---- fused gather: the read's probe records of this strand in a register window
 			// (probe pb is rx[0]/ry[0]; advancing shifts the window), candidates generated in
@@ -703,6 +724,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SVG_LAN
 				if (j + 4 < mycnt) { q3 = lval(lp, next(it, pkn), it); k3 = pkn; }
 				if (j < mycnt && !L.dfr) L.template vote<0>(st, val - (pk >> 6), (int)(pk & 63u), (int)(pk >> 6), high_b, lp.gap);
 			}
+			if (lp.stats) nvstep += (uint32_t)__builtin_amdgcn_readfirstlane(mc);
+			}
+			if (lp.stats) {
+				// the strand's tail (gate, top-3, row-major scans) runs to the wave's largest table
+				int ms = L.dfr ? 0 : L.nslots;
+				for (int o = 32; o; o >>= 1) { int t = __shfl_xor(ms, o); ms = t > ms ? t : ms; }
+				ntstep += (uint32_t)__builtin_amdgcn_readfirstlane(ms);
 			}
 			if (L.dfr) continue;
 			// ---- SE gate (core.c:3215-3233) and top-K (core-junction.c:2199-2530, ends = 1)
@@ -965,6 +993,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SVG_LAN
 			atomicAdd(&d[2], nwhy3);
 			atomicAdd(&d[3], ncand);
 			atomicAdd(&d[4], ndef);
+			// words 28 / 29: vote-loop steps and tail steps of all waves; lane utilisation of the
+			// vote loop = d[3] / (64 * stats[28])
+			atomicAdd(&lp.stats[28], (unsigned long long)nvstep);
+			atomicAdd(&lp.stats[29], (unsigned long long)ntstep);
 		}
 	}
 }
@@ -1491,24 +1523,35 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) la
 // ---------------------------------------------------------------------------------------------
 // count bins (fused SE path): thread per read, the same eligibility tests and per-strand
 // candidate counts the lane kernel starts with (its probe records, SoA); reads past the lane
-// limits go straight to the deferral list, the rest to bin lbin_of(larger strand count)
+// limits go straight to the deferral list, the rest to the list of their heavier strand and its
+// count class, lbin_of(larger strand count)
 // ---------------------------------------------------------------------------------------------
-// Block tiles of LBT consecutive reads: the tile's lists are built in LDS (local offsets), then
-// one global atomic per list and tile reserves the output range (per-wave global atomics on five
-// counters serialised the kernel), and each list goes out in the tile's read order.
-#define LBT 1024   // 4 rounds of 256 reads per tile, ~4 tiles per CU at 1M reads (latency hidden across blocks)
+// Block tiles of LBT consecutive reads, one counting sort in LDS per tile: a read's key is its list
+// and, with LLIGHT > 1, the class of its lighter strand's count inside the list.  A list holds whole
+// tiles one after the other, so a group's probe record loads stay within a few tiles.  One global
+// atomic per list and tile reserves the output range (per-wave global atomics on five counters
+// serialised the kernel).
+#ifndef LBT
+// 4 rounds of 256 reads per tile, ~4 tiles per CU at 1M reads (latency hidden across blocks); tiles
+// of 4096 reads with 1024 threads made this kernel 12 ms per C3 step slower
+#define LBT 1024
+#define LBTHREADS 256
+#endif
+#define LBKEYS (LLISTS * LLIGHT + 1)   // the last key: deferred
 template <int NPF>
-__global__ void __launch_bounds__(256) lane_bin_kernel(LParams lp)
+__global__ void __launch_bounds__(LBTHREADS) lane_bin_kernel(LParams lp)
 {
-	__shared__ uint16_t lst[LBINS + 1][LBT];   // list LBINS: deferred
-	__shared__ uint32_t lcnt[LBINS + 1], gbase[LBINS + 1];
-	const int lane = (int)__lane_id(), tid = (int)threadIdx.x;
+	__shared__ uint16_t ord[LBT];              // the tile's reads (local offsets) in key order
+	__shared__ uint32_t hist[LBKEYS], kstart[LBKEYS], lcnt[LLISTS + 1], gbase[LLISTS + 1];
+	const int tid = (int)threadIdx.x;
 	unsigned long long ndef = 0;
 	for (uint32_t t0 = blockIdx.x * LBT; t0 < lp.n; t0 += gridDim.x * LBT) {
-		if (tid <= LBINS) lcnt[tid] = 0;
+		if (tid < LBKEYS) hist[tid] = 0;
 		__syncthreads();
-		for (int i = 0; i < LBT / 256; i++) {
-			const uint32_t loc = (uint32_t)(i * 256 + tid), r = t0 + loc;
+		uint32_t kr[LBT / LBTHREADS];          // key << 16 | rank inside the key (0xffffffff: no read)
+#pragma unroll
+		for (int i = 0; i < LBT / LBTHREADS; i++) {
+			const uint32_t loc = (uint32_t)(i * LBTHREADS + tid), r = t0 + loc;
 			const bool live = r < lp.n;
 			int len = live ? lp.len[r] : 0;
 			if (len > SVG_READ_KEEP) len = SVG_READ_KEEP;
@@ -1522,7 +1565,7 @@ __global__ void __launch_bounds__(256) lane_bin_kernel(LParams lp)
 			}
 			if (len < 15 + lp.gap || len > 160 || applied > 31 || applied * lp.gap > NPF || applied * lp.gap > lp.nps) dfr = true;
 			const int np = applied * lp.gap;
-			int mx = 0;
+			int mx = 0, mn = 0, hv = 0;
 #pragma unroll
 			for (int st = 0; st < 2; st++) {
 				int cnt = 0;
@@ -1531,35 +1574,44 @@ __global__ void __launch_bounds__(256) lane_bin_kernel(LParams lp)
 					const uint32_t y = live && !dfr && p < np ? lp.precs[(size_t)(st * lp.nps + p) * lp.n + r].y : 0u;
 					cnt += (int)((y & 0xffffu) + (y >> 16));
 				}
-				mx = cnt > mx ? cnt : mx;
+				if (st == 0) { mx = cnt; mn = cnt; }
+				else if (cnt > mx) { mx = cnt; hv = 1; }
+				else mn = cnt;
 			}
 			if (mx > lp.cap) dfr = true;
-			const int cl = dfr ? LBINS : lbin_of(mx);
+			const int key = dfr ? LBKEYS - 1 : lp.bin_rule ? 2 * lbin_of(mx) * LLIGHT
+			                                               : (2 * lbin_of(mx) + hv) * LLIGHT + llight_of(mn);
+			kr[i] = live ? ((uint32_t)key << 16) | atomicAdd(&hist[key], 1u) : 0xffffffffu;
+		}
+		__syncthreads();
+		if (tid < LBKEYS) {
+			uint32_t a = 0;
+			for (int q = 0; q < tid; q++) a += hist[q];
+			kstart[tid] = a;
+		}
+		if (tid <= LLISTS) {
+			uint32_t c = 0;
+			for (int q = tid * LLIGHT; q < (tid + 1) * LLIGHT && q < LBKEYS; q++) c += hist[q];
+			lcnt[tid] = c;
+			gbase[tid] = c ? atomicAdd(tid == LLISTS ? lp.defer_count : &lp.bin_count[tid], c) : 0u;
+		}
+		__syncthreads();
 #pragma unroll
-			for (int q = 0; q <= LBINS; q++) {
-				const unsigned long long bm = __ballot(live && cl == q);
-				if (!bm) continue;
-				const int leader = __ffsll((long long)bm) - 1;
-				uint32_t base = 0;
-				if (lane == leader) base = atomicAdd(&lcnt[q], (uint32_t)__popcll(bm));
-				base = __shfl(base, leader);
-				if (live && cl == q) lst[q][base + __popcll(bm & ((1ull << lane) - 1ull))] = (uint16_t)loc;
+		for (int i = 0; i < LBT / LBTHREADS; i++)
+			if (kr[i] != 0xffffffffu) ord[kstart[kr[i] >> 16] + (kr[i] & 0xffffu)] = (uint16_t)(i * LBTHREADS + tid);
+		__syncthreads();
+		for (int q = 0; q <= LLISTS; q++) {
+			const uint32_t c = lcnt[q], s0 = kstart[q * LLIGHT], gb = gbase[q];
+			if (q == LLISTS) {
+				for (uint32_t j = (uint32_t)tid; j < c; j += LBTHREADS) lp.defer_list[gb + j] = t0 + ord[s0 + j];
+			} else {
+				// strand 0's list of a class grows up from the class's start, strand 1's down from its end
+				uint32_t *cls = lp.bins + (size_t)(q >> 1) * lp.n;
+				for (uint32_t j = (uint32_t)tid; j < c; j += LBTHREADS) cls[(q & 1) ? lp.n - 1u - (gb + j) : gb + j] = t0 + ord[s0 + j];
 			}
 		}
-		__syncthreads();
-		if (tid <= LBINS) {
-			const uint32_t c = lcnt[tid];
-			gbase[tid] = c ? atomicAdd(tid == LBINS ? lp.defer_count : &lp.bin_count[tid], c) : 0u;
-		}
-		__syncthreads();
-#pragma unroll
-		for (int q = 0; q <= LBINS; q++) {
-			const uint32_t c = lcnt[q];
-			uint32_t *dst = (q == LBINS ? lp.defer_list : lp.bins + (size_t)q * lp.n) + gbase[q];
-			for (uint32_t j = (uint32_t)tid; j < c; j += 256u) dst[j] = t0 + lst[q][j];
-		}
-		ndef += lcnt[LBINS];
-		__syncthreads();   // lcnt / lst are reused by the next tile
+		ndef += lcnt[LLISTS];
+		__syncthreads();   // hist / ord / lcnt are reused by the next tile
 	}
 	if (lp.stats && tid == 0 && ndef) {
 		if (lp.final_pass) atomicAdd(&lp.stats[4], ndef);
@@ -1747,9 +1799,9 @@ int svg_lane_chunk(svg_index *h, int slot, const svg_params *p, const uint16_t *
 		h->lane_cap[slot] = need;
 	}
 	uint8_t *b = (uint8_t *)h->d_lane[slot];
-	// [0] deferrals, [2] wave-kernel work counter, [4..7] count-bin sizes
+	// [0] deferrals, [2] wave-kernel work counter, [4..4 + LLISTS) count-bin list sizes
 	uint32_t *cnt = (uint32_t *)(b + o_cnt);
-	HIPCHK(hipMemsetAsync(cnt, 0, 32, st));
+	HIPCHK(hipMemsetAsync(cnt, 0, 4 * (4 + LLISTS), st));
 	GParams g;
 	g.precs = precs; g.len = len; g.vals = h->dix.vals; g.n = n; g.nps = nps; g.gap = h->dix.gap;
 	g.total_subreads = p->total_subreads; g.cap = LANE_CAP1;
@@ -1792,21 +1844,25 @@ int svg_lane_chunk(svg_index *h, int slot, const svg_params *p, const uint16_t *
 	lp.final_pass = 1;
 	lp.cs = n; lp.idx = NULL; lp.idx_count = NULL;
 	lp.bins = NULL; lp.bin_count = NULL;
+	// option lane_bins: 0 lists by heavier strand and its count class; 1 one list per class of the
+	// larger strand count (the earlier rule)
+	lp.bin_rule = svg_get_option("lane_bins") == 1;
 	{
-		// option lane_cap: candidates per strand (<= 64 fused); lane_bin 2: no count bins
+		// option lane_cap: candidates per strand (<= 64 fused)
 		const int oc = (int)svg_get_option("lane_cap");
 		if (oc > 0 && oc <= LANE_CAP1) lp.cap = oc;
 		if (oc > LANE_CAP1 && fused) lp.cap = oc < 64 ? oc : 64;
 		// count bins for the fused single-pass path: one thread per read sorts the chunk's reads into
-		// LBINS lists by candidate count (and defers the over-cap ones) before the lane kernel
+		// LLISTS lists (and defers the over-cap ones) before the lane kernel; the two lists of a
+		// class share n entries, so the lists take 4 * LBINS * n bytes whatever the rule
 		if (fused) {
 			lp.bins = (uint32_t *)(b + o_bin);
 			lp.bin_count = cnt + 4;
 			uint64_t bb = ((uint64_t)n + LBT - 1) / LBT, bmax = (uint64_t)h->n_cu * 8;
 			if (bb > bmax) bb = bmax;
 			if (bb < 1) bb = 1;
-			if (sjm) hipLaunchKernelGGL(lane_bin_kernel<LANE_NPF_SJ>, dim3((unsigned)bb), dim3(256), 0, st, lp);
-			else hipLaunchKernelGGL(lane_bin_kernel<LANE_NPF>, dim3((unsigned)bb), dim3(256), 0, st, lp);
+			if (sjm) hipLaunchKernelGGL(lane_bin_kernel<LANE_NPF_SJ>, dim3((unsigned)bb), dim3(LBTHREADS), 0, st, lp);
+			else hipLaunchKernelGGL(lane_bin_kernel<LANE_NPF>, dim3((unsigned)bb), dim3(LBTHREADS), 0, st, lp);
 			HIPCHK(hipGetLastError());
 		}
 		if (!fused) rc = lane_launch<LANE_K1_WIDE, 0>(h, lp, &h->d_lscratch, &h->lscratch_words, st);

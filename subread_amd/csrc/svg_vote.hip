@@ -3287,7 +3287,9 @@ extern "C" int svg_set_stats(svg_index *h, int enable)
 // debug: raw device counters (32 words; 8..15 = per-phase wave cycles in SVG_STAMPS builds,
 // 16..20 = light lane pass: deferrals by reason (candidates > CAP or length, slots > K,
 // shift-indel), candidates voted, deferrals; 21..25 = the same for the heavy lane pass;
-// 26 / 27 = wave-kernel candidates settled by batch mode / replayed serially)
+// 26 / 27 = wave-kernel candidates settled by batch mode / replayed serially; 28 / 29 = lane_kernel
+// wave steps: vote loop (per group and strand, the largest candidate count of a lane) and tail
+// (the largest slot count); [19] / (64 * [28]) is the vote loop's lane utilisation)
 extern "C" int svg_debug_counters(svg_index *h, unsigned long long *out32)
 {
 	if (!h || !out32) return SVG_E_ARG;

@@ -42,6 +42,15 @@ def main():
     for name, b in (("light", 16), ("heavy", 21)):
         print("  %s pass: deferred %d (cap/length %d, slots %d, shift-indel %d), candidates voted %d" % (
             name, dc[b + 4], dc[b], dc[b + 1], dc[b + 2], dc[b + 3]))
+    if r2 is None:
+        # lane_kernel's lockstep steps under both count-bin rules (option lane_bins; tools/lane_bin_model.py)
+        for rule in (0, 1):
+            sa.set_option("lane_bins", rule)
+            ix.vote(default_params(prog, False), r, None)
+            dc = ix.debug_counters()
+            print("  lane_bins %d: vote-loop steps %d, tail steps %d, candidates %d, deferred %d, lane utilisation %.3f" % (
+                rule, dc[28], dc[29], dc[19], dc[20], dc[19] / (64.0 * max(dc[28], 1))), flush=True)
+        sa.set_option("lane_bins", 0)
     ix.close()
 
 
