@@ -196,9 +196,14 @@ void svg_index_close(svg_index *idx);
 int  svg_index_get_info(const svg_index *idx, svg_index_info *out);
 
 /*
- * Build a single-block index straight into HBM (same bytes as svg_build_index /
- * subread-buildindex), from a FASTA file or from in-memory contigs; when
- * save_prefix is not NULL the reference-format files are also written there.
+ * Build an index straight into HBM, from a FASTA file or from in-memory contigs, with the block
+ * structure subread-buildindex gives it for `memory_mb` (-M): one block if force_one_block (-B)
+ * is set or no block ever closes, else as many as build_gene_index splits off (at most 64: beyond
+ * that SVG_E_UNSUPPORTED).  Every block stays resident, as after svg_index_open;
+ * svg_index_get_info().n_blocks reports their number.  The items are those of svg_build_index /
+ * subread-buildindex; when save_prefix is not NULL the reference-format files of every block
+ * (and .reads / .files / .log) are also written there, and blocks a previous build left behind
+ * are removed.
  */
 int  svg_index_build(const char *fasta, int gap, int memory_mb, int force_one_block,
                      int repeat_threshold, int device, const char *save_prefix, svg_index **out);

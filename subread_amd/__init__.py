@@ -433,7 +433,9 @@ class VoteIndex:
     @classmethod
     def build(cls, fasta, gap=1, memory_mb=8000, force_one_block=True, repeat_threshold=100, device=0,
               save_prefix=None):
-        """Build the index in HBM (GPU builder); optionally also write the reference files."""
+        """Build the index in HBM (GPU builder) with the block structure subread-buildindex gives it
+        for memory_mb: one block if force_one_block is set or no block ever closes, else several
+        (n_blocks), all resident.  save_prefix: also write every block's reference-format files."""
         h = ctypes.c_void_p()
         _check(lib().svg_index_build(str(fasta).encode(), gap, memory_mb, 1 if force_one_block else 0,
                                      repeat_threshold, device, save_prefix.encode() if save_prefix else None,
@@ -443,7 +445,7 @@ class VoteIndex:
     @classmethod
     def build_genome(cls, genome, gap=1, memory_mb=8000, force_one_block=True, repeat_threshold=100, device=0,
                      save_prefix=None):
-        """Build from a subread_amd.sim.Genome (in-memory contigs)."""
+        """VoteIndex.build from a subread_amd.sim.Genome (in-memory contigs): one block or several."""
         n = len(genome.seqs)
         names = (ctypes.c_char_p * n)(*[x.encode() for x in genome.names])
         seqs = (ctypes.c_void_p * n)(*[s.ctypes.data for s in genome.seqs])

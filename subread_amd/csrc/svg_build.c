@@ -203,8 +203,8 @@ uint64_t svg_items_budget(int gap, int memory_mb, int force_one_block)
 	return (uint32_t)(memory_mb * 1024.0 / 8.) * 1024;
 }
 
-static int write_tab_block(const char *prefix, int block, uint32_t nb, uint64_t items, int gap, const uint32_t *bstart,
-                           const int16_t *keys, const uint32_t *vals)
+int svg_write_tab_block(const char *prefix, int block, uint32_t nb, uint64_t items, int gap, const uint32_t *bstart,
+                        const int16_t *keys, const uint32_t *vals)
 {
 	char fn[4096];
 	FILE *fp;
@@ -244,14 +244,8 @@ static int write_tab_block(const char *prefix, int block, uint32_t nb, uint64_t 
 	return rc;
 }
 
-int svg_write_tab(const char *prefix, uint32_t nb, uint64_t items, int gap, const uint32_t *bstart,
-                  const int16_t *keys, const uint32_t *vals)
-{
-	return write_tab_block(prefix, 0, nb, items, gap, bstart, keys, vals);
-}
-
 /* blocks a previous build into the same prefix left behind (build_gene_index, index-builder.c:181-187) */
-static void unlink_blocks_from(const char *prefix, int first)
+void svg_unlink_blocks_from(const char *prefix, int first)
 {
 	char fn[4096];
 	int i;
@@ -283,7 +277,31 @@ uint8_t *svg_pack_array(const genome_t *g, const uint64_t *O, uint32_t *length_o
 	return arr;
 }
 
-static int write_array_block(const char *prefix, int block, uint32_t start, uint32_t length, const uint8_t *arr, size_t vb)
+/* one block's .array image (gvindex_set over the block's segments): the bases from each segment's
+ * first window to its last window + 16, or to the contig's end where the segment ends its contig;
+ * packed from start - start % 4; length / values_bytes as gvindex_load computes them */
+uint8_t *svg_pack_array_block(const genome_t *g, const uint64_t *O, uint64_t start, uint64_t last_set, const svg_bp_seg *seg,
+                              uint32_t nseg, uint32_t *length_out, uint32_t *vbytes_out)
+{
+	const uint64_t sbo = start - start % 4;
+	const uint32_t length = (uint32_t)(last_set + 16 - start + PAD);
+	const size_t vb = (size_t)((length + start - sbo) >> 2) + 1;
+	uint8_t *arr = calloc(vb + 64, 1);
+	uint32_t s;
+	if (!arr) return NULL;
+	for (s = 0; s < nseg; s++) {
+		const svg_bp_seg *S = &seg[s];
+		const char *base = g->bases + g->ctg[S->c].start;
+		const uint64_t set_end = S->ends ? O[S->c] + g->ctg[S->c].len : S->b + 16;
+		uint64_t p;
+		for (p = S->a; p < set_end; p++) arr[(p - sbo) >> 2] |= (uint8_t)(b2i(base[p - O[S->c]]) << (2 * (p & 3)));
+	}
+	*length_out = length;
+	*vbytes_out = (uint32_t)vb;
+	return arr;
+}
+
+int svg_write_array_block(const char *prefix, int block, uint32_t start, uint32_t length, const uint8_t *arr, size_t vb)
 {
 	char fn[4096];
 	FILE *fp;
@@ -298,8 +316,8 @@ static int write_array_block(const char *prefix, int block, uint32_t start, uint
 }
 
 /* .reads / .files / .log (the genome-wide files of any build) */
-static int write_reads_files(const char *prefix, const genome_t *g, const uint64_t *O, int gap, uint64_t nwin,
-                             uint64_t items, uint32_t nb, int nblocks, const char *source)
+int svg_write_reads_files(const char *prefix, const genome_t *g, const uint64_t *O, int gap, uint64_t nwin,
+                          uint64_t items, uint32_t nb, int nblocks, const char *source)
 {
 	char fn[4096];
 	FILE *fp;
@@ -329,11 +347,11 @@ int svg_write_array_reads(const char *prefix, const genome_t *g, const uint64_t 
 	int rc;
 	uint8_t *arr = svg_pack_array(g, O, &length, &vb);
 	if (!arr) { svg_set_error("out of memory packing .array"); return SVG_E_NOMEM; }
-	rc = write_array_block(prefix, 0, 0, length, arr, vb);
+	rc = svg_write_array_block(prefix, 0, 0, length, arr, vb);
 	free(arr);
 	if (rc) return rc;
-	unlink_blocks_from(prefix, 1);
-	return write_reads_files(prefix, g, O, gap, nwin, items, nb, 1, source);
+	svg_unlink_blocks_from(prefix, 1);
+	return svg_write_reads_files(prefix, g, O, gap, nwin, items, nb, 1, source);
 }
 
 /* sorted (key << 32 | pa) items -> bucket layout -> <prefix>.NN.b.tab (gehash_dump,
@@ -362,7 +380,7 @@ static int tab_from_sorted(const char *prefix, int block, uint32_t nb, const uin
 		vals[d] = ((key % 791) % 2 == 0) ? pa : ~pa;
 	}
 	free(cur);
-	rc = write_tab_block(prefix, block, nb, n, gap, bstart, keys, vals);
+	rc = svg_write_tab_block(prefix, block, nb, n, gap, bstart, keys, vals);
 	free(bstart); free(keys); free(vals);
 	return rc;
 }
@@ -400,11 +418,11 @@ static int is_repeat(const uint32_t *rep, uint64_t nrep, uint32_t key)
  * (start_point = the block's first window; the bases its windows and contig-end writes covered,
  * gvindex_set / gvindex_dump, gene-value-index.c:135-187).
  */
-typedef struct { uint32_t c; uint64_t a, b; int ends; } seg_t;
-typedef struct { uint64_t start, last_set, items; uint32_t s0, ns; } blk_t;
+typedef svg_bp_seg seg_t;
+typedef svg_bp_block blk_t;
 
-#define MIN_READ_SPLICING 2000000u
-#define SPLICE_BACK (MIN_READ_SPLICING - 10 - (MIN_READ_SPLICING - 10) % 3 + 1 - 16)
+#define MIN_READ_SPLICING SVG_BP_MIN_READ_SPLICING
+#define SPLICE_BACK SVG_BP_SPLICE_BACK
 
 static int build_blocks(const char *prefix, const genome_t *g, const uint64_t *O, int gap, uint32_t nb, uint64_t budget,
                         const uint32_t *rep, uint64_t nrep, int *nblocks_out)
@@ -450,31 +468,26 @@ static int build_blocks(const char *prefix, const genome_t *g, const uint64_t *O
 	for (k = 0; k < nblk && !rc; k++) {
 		const blk_t *B = &blk[k];
 		uint64_t *items = malloc(sizeof(uint64_t) * (B->items + 1)), *tmp = malloc(sizeof(uint64_t) * (B->items + 1)), n = 0;
-		const uint64_t sbo = B->start - B->start % 4;
-		const uint32_t length = (uint32_t)(B->last_set + 16 - B->start + PAD);
-		const size_t vb = (size_t)((length + B->start - sbo) >> 2) + 1;
-		uint8_t *arr = calloc(vb + 8, 1);
-		uint32_t s;
+		uint32_t length = 0, vb = 0, s;
+		uint8_t *arr = svg_pack_array_block(g, O, B->start, B->last_set, seg + B->s0, B->ns, &length, &vb);
 		if (!items || !tmp || !arr) { free(items); free(tmp); free(arr); rc = SVG_E_NOMEM; svg_set_error("out of memory (block %u)", k); break; }
 		for (s = B->s0; s < B->s0 + B->ns; s++) {
 			const seg_t *S = &seg[s];
 			const char *base = g->bases + g->ctg[S->c].start;
-			const uint64_t set_end = S->ends ? O[S->c] + g->ctg[S->c].len : S->b + 16;
 			uint64_t p;
 			for (p = S->a; p <= S->b; p += gap) {
 				uint32_t key = window_key(base + (p - O[S->c]));
 				if (!is_repeat(rep, nrep, key)) items[n++] = window_item(key, (uint32_t)p);
 			}
-			for (p = S->a; p < set_end; p++) arr[(p - sbo) >> 2] |= (uint8_t)(b2i(base[p - O[S->c]]) << (2 * (p & 3)));
 		}
 		radix64(items, tmp, n);
 		free(tmp);
 		rc = tab_from_sorted(prefix, (int)k, nb, items, n, gap);
 		free(items);
-		if (!rc) rc = write_array_block(prefix, (int)k, (uint32_t)B->start, length, arr, vb);
+		if (!rc) rc = svg_write_array_block(prefix, (int)k, (uint32_t)B->start, length, arr, vb);
 		free(arr);
 	}
-	if (!rc) unlink_blocks_from(prefix, (int)nblk);
+	if (!rc) svg_unlink_blocks_from(prefix, (int)nblk);
 	*nblocks_out = (int)nblk;
 out:
 	free(seg); free(blk);
@@ -545,7 +558,7 @@ int svg_build_index(const char *fasta, const char *prefix, int gap, int memory_m
 		free(items); items = NULL;
 		free(tmp); tmp = NULL;
 		rc = build_blocks(prefix, &g, O, gap, nb, budget, rep, nrep, &nblocks);
-		if (!rc) rc = write_reads_files(prefix, &g, O, gap, nwin, nkeep, nb, nblocks, fasta);
+		if (!rc) rc = svg_write_reads_files(prefix, &g, O, gap, nwin, nkeep, nb, nblocks, fasta);
 		goto out;
 	}
 	if (nkeep > 0xffffffffull) { rc = SVG_E_UNSUPPORTED; svg_set_error("more than 2^32-1 items"); goto out; }

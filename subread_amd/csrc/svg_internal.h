@@ -5,6 +5,7 @@
 #include "subread_vote.h"
 #include "subread_events.h"
 #include "subread_realign.h"
+#include "svg_blockplan.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -83,12 +84,21 @@ void svg_genome_free(svg_genome *g);
 void svg_genome_layout(const svg_genome *g, int gap, uint64_t *O, uint64_t *nwin);
 uint64_t svg_items_budget(int gap, int memory_mb, int force_one_block);
 /* writers of the reference on-disk format */
-int svg_write_tab(const char *prefix, uint32_t nb, uint64_t items, int gap, const uint32_t *bstart,
-                  const int16_t *keys, const uint32_t *vals);
 int svg_write_array_reads(const char *prefix, const svg_genome *g, const uint64_t *O, int gap,
                           uint64_t nwin, uint64_t items, uint32_t nb, const char *source);
 /* 2-bit LSB-first .array image (gvindex_set), length/values_bytes as gvindex_load sees them */
 uint8_t *svg_pack_array(const svg_genome *g, const uint64_t *O, uint32_t *length, uint32_t *values_bytes);
+/* the same for one block of a multi-block index (svg_blockplan.h: the block's segments), as
+ * svg_host.c's loader leaves it for <prefix>.NN.b.array; shared by the CPU and the GPU builder */
+uint8_t *svg_pack_array_block(const svg_genome *g, const uint64_t *O, uint64_t start, uint64_t last_set,
+                              const svg_bp_seg *seg, uint32_t nseg, uint32_t *length, uint32_t *values_bytes);
+/* per-block and genome-wide files of a build, and the removal of a previous build's blocks */
+int svg_write_tab_block(const char *prefix, int block, uint32_t nb, uint64_t items, int gap, const uint32_t *bstart,
+                        const int16_t *keys, const uint32_t *vals);
+int svg_write_array_block(const char *prefix, int block, uint32_t start, uint32_t length, const uint8_t *arr, size_t vb);
+int svg_write_reads_files(const char *prefix, const svg_genome *g, const uint64_t *O, int gap, uint64_t nwin,
+                          uint64_t items, uint32_t nb, int nblocks, const char *source);
+void svg_unlink_blocks_from(const char *prefix, int first);
 
 #ifdef __cplusplus
 }
