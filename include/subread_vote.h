@@ -269,6 +269,72 @@ int svg_probe_keys_device(svg_index *idx, int block, const uint32_t *keys, uint6
                           uint32_t *first, uint32_t *count, void *hip_stream);
 
 /*
+ * cellCounts' voting step for a batch of reads (cellCounts_do_voting, cell-counts.c:3051-3131, up
+ * to the call of cellCounts_select_and_write_alignments).  Per read the reference looks up every
+ * subread of both strands (prefill_votes, :3085-3101: one key per subread at offset
+ * (step * k) >> 16, no gap-slot loop) and then tallies the hit lists into a private 17-row x
+ * 3-slot table shared by both strands (cellCounts_process_copy_ptrs_to_votes, :2786-2881:
+ * subreads in ascending order of hit count under quick_sort_run's permutation, core.c:4694-4714;
+ * hits of a run visited at (sum += 66889) % run; the indel recorder keyed by distance).  Nothing
+ * outside the read is touched, so the step is a function of the read, the one-block index,
+ * total_subreads and max_indel_length: svg_cell_vote_batch runs it on the GPU and returns the
+ * tables (host buffers, synchronous; the result arrays are owned by the library until
+ * svg_cell_vote_free).
+ *   total_subreads    --subreadsPerRead, 7..20 (the reference's clamp, :547); default 10
+ *   max_indel_length  5: cellCounts' option parsing never changes it (:521)
+ * Other values are SVG_E_ARG, as is a read of more than SVG_CELL_MAX_READ_LENGTH bases; an index
+ * of several blocks is SVG_E_UNSUPPORTED (cellCounts refuses it, :641-644).  A read under 16
+ * bases gets a zero head and no slots (:3077).
+ * Limit: the tables are the reference's for indexes whose hit lists (equal-key runs) hold at most
+ * 32,000 items.  Past that the reference's int sum of 66889 * run overflows and it reads before
+ * the list; here the sum is unsigned and stays inside the list.  subread-buildindex's default
+ * repeat threshold (-f 100) keeps every list under 100 items.
+ * A caller fills a gene_sc_vote_t (cell-counts.c:37-64) field by field: max_vote and items[]
+ * from the head; pos, masks, votes, toli, coverage_start / _end and indel_recorder[0..toli) of
+ * slot [row][k] from slots[first_slot + items[0] + .. + items[row-1] + k].  Fields the tally never
+ * writes (quality, cursors, the max_* fields but max_vote, recorder entries past toli) are not
+ * part of the result.
+ */
+#define SVG_CELL_ROWS             17    /* GENE_SCRNA_VOTE_TABLE_SIZE */
+#define SVG_CELL_SPACE            3     /* GENE_SCRNA_VOTE_SPACE */
+#define SVG_CELL_RECORDER         21    /* MAX_INDEL_TOLERANCE * 3 */
+#define SVG_CELL_MAX_READ_LENGTH  160   /* MAX_SCRNA_READ_LENGTH */
+
+typedef struct svg_cell_params {
+	int32_t total_subreads;
+	int32_t max_indel_length;
+} svg_cell_params;
+
+typedef struct svg_cell_head {
+	uint64_t first_slot;              /* the read's first record in slots */
+	uint16_t n_slots;                 /* sum of items[] */
+	int16_t  max_vote;
+	int16_t  applied_subreads;        /* per strand; 0 for a read under 16 bases */
+	uint8_t  items[SVG_CELL_ROWS];
+	uint8_t  _pad;
+} svg_cell_head;                      /* 32 bytes */
+
+typedef struct svg_cell_slot {
+	uint32_t pos;
+	int16_t  mask;                    /* 0, or IS_NEGATIVE_STRAND (2048) */
+	int16_t  votes;
+	int16_t  coverage_start, coverage_end;
+	uint8_t  toli;
+	uint8_t  _pad;
+	int16_t  indel_recorder[SVG_CELL_RECORDER];   /* zero from toli on */
+} svg_cell_slot;                      /* 56 bytes */
+
+typedef struct svg_cell_votes {
+	uint64_t n_reads, n_slots;
+	svg_cell_head *heads;             /* one per read, batch order */
+	svg_cell_slot *slots;             /* read by read, each read's in row-major slot order */
+} svg_cell_votes;
+
+int  svg_cell_vote_batch(svg_index *idx, const svg_cell_params *p, const svg_packed_reads *reads,
+                         svg_cell_votes *res);
+void svg_cell_vote_free(svg_cell_votes *res);
+
+/*
  * Fragile junction voting of subjunc reads longer than 160 bases (core_fragile_junction_voting,
  * core-junction.c:5151-5422; do_voting runs it for every index block, strand and read end,
  * core.c:3138-3142).  The read (strand 0: as fetched after the -S reversal, strand 1: its

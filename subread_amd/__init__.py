@@ -16,7 +16,7 @@ import numpy as np
 
 from .abi import (MAPPING_DTYPE, SUBJUNC_DTYPE, BIG_MARGIN_WORDS, ERRORS, PROGRAM_ALIGN,
                   PROGRAM_SUBJUNC, SvgParams, SvgReads, SvgPackedReads, SvgIndexInfo, SvgBatchStats, ReadBatch,
-                  SvgFragileResult,
+                  SvgFragileResult, SvgCellParams, SvgCellVotes, CELL_HEAD_DTYPE, CELL_SLOT_DTYPE,
                   PackedBatch, default_params, read_fastq)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -33,6 +33,7 @@ EXPORTS = [
     "svg_get_kernel_timing", "svg_device_status", "svg_pack_reads", "svg_vote_batch_packed",
     "svg_vote_batch_packed_device", "svg_probe_keys", "svg_probe_keys_device", "svg_host_threads",
     "svg_fragile_batch", "svg_fragile_free", "svg_set_option", "svg_get_option",
+    "svg_cell_vote_batch", "svg_cell_vote_free",
     "svg_host_placement", "svg_host_alloc", "svg_host_free", "svg_cpulist_parse",
     # sublong's voting step (include/subread_long.h)
     "svg_long_vote_batch", "svg_long_free",
@@ -145,6 +146,9 @@ def lib():
         L.svg_fragile_batch.argtypes = [vp] * 5
         L.svg_fragile_batch.restype = i32
         L.svg_fragile_free.argtypes = [vp]
+        L.svg_cell_vote_batch.argtypes = [vp] * 4
+        L.svg_cell_vote_batch.restype = i32
+        L.svg_cell_vote_free.argtypes = [vp]
         if hasattr(L, "svg_long_vote_batch"):   # (older builds loaded side by side for A/B runs lack it)
             L.svg_long_vote_batch.argtypes = [vp] * 3
             L.svg_long_vote_batch.restype = i32
@@ -525,6 +529,21 @@ class VoteIndex:
             return res.arrays()
         finally:
             lib().svg_fragile_free(ctypes.byref(res))
+
+    def cell_vote(self, packed_reads, total_subreads=10, max_indel_length=5):
+        """svg_cell_vote_batch: cellCounts' voting step (cellCounts_do_voting's lookups and
+        cellCounts_process_copy_ptrs_to_votes, cell-counts.c:3051-3131, :2786-2881) for a PackedBatch
+        -> (heads, slots): one CELL_HEAD_DTYPE per read and the used slots of every read's 17 x 3
+        table as CELL_SLOT_DTYPE, in table order, read i's at slots[first_slot : first_slot + n_slots]."""
+        p = SvgCellParams(int(total_subreads), int(max_indel_length))
+        s = packed_reads.struct()
+        res = SvgCellVotes()
+        rc = lib().svg_cell_vote_batch(self.h, ctypes.byref(p), ctypes.byref(s), ctypes.byref(res))
+        _check(rc, "svg_cell_vote_batch")
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_vote_free(ctypes.byref(res))
 
     def long_vote(self, reads):
         """svg_long_vote_batch: sublong's voting step (LRMdo_one_voting_read + the copy and location

@@ -160,6 +160,36 @@ class SvgFragileResult(ctypes.Structure):
         return r
 
 
+# svg_cell_head / svg_cell_slot (include/subread_vote.h): cellCounts' per-read vote table
+# (gene_sc_vote_t, cell-counts.c:37-64) as svg_cell_vote_batch returns it
+CELL_ROWS, CELL_SPACE, CELL_MAX_READ_LENGTH = 17, 3, 160
+CELL_HEAD_DTYPE = np.dtype([("first_slot", "<u8"), ("n_slots", "<u2"), ("max_vote", "<i2"),
+                            ("applied_subreads", "<i2"), ("items", "u1", (CELL_ROWS,)), ("_pad", "u1")])
+CELL_SLOT_DTYPE = np.dtype([("pos", "<u4"), ("mask", "<i2"), ("votes", "<i2"), ("coverage_start", "<i2"),
+                            ("coverage_end", "<i2"), ("toli", "u1"), ("_pad", "u1"),
+                            ("indel_recorder", "<i2", (21,))])
+assert CELL_HEAD_DTYPE.itemsize == 32 and CELL_SLOT_DTYPE.itemsize == 56
+
+
+class SvgCellParams(ctypes.Structure):
+    _fields_ = [("total_subreads", ctypes.c_int32), ("max_indel_length", ctypes.c_int32)]
+
+
+class SvgCellVotes(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint64), ("n_slots", ctypes.c_uint64),
+                ("heads", ctypes.c_void_p), ("slots", ctypes.c_void_p)]
+
+    def arrays(self):
+        """Copies of the heads and slots as numpy structured arrays."""
+        h = np.zeros(self.n_reads, dtype=CELL_HEAD_DTYPE)
+        s = np.zeros(self.n_slots, dtype=CELL_SLOT_DTYPE)
+        if self.n_reads:
+            ctypes.memmove(h.ctypes.data, self.heads, h.nbytes)
+        if self.n_slots:
+            ctypes.memmove(s.ctypes.data, self.slots, s.nbytes)
+        return h, s
+
+
 # svg_long_vote (include/subread_long.h): one used slot of sublong's LRMgene_vote_t
 LONG_VOTE_DTYPE = np.dtype([("pos", "<u4"), ("coverage_start", "<u4"), ("coverage_end", "<u4"),
                             ("votes", "<u2"), ("negative", "u1"), ("_pad", "u1"), ("slot", "<u4")])
