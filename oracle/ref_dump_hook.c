@@ -219,3 +219,168 @@ int __wrap_init_bigtable_results(global_context_t *gc, int is_rewinding)
 	if (!is_rewinding && e && atol(e) > 0) gc->config.reads_per_chunk = atol(e);
 	return __real_init_bigtable_results(gc, is_rewinding);
 }
+
+#ifdef SVG_HOOK_FRAGILE
+/*
+ * Fragile-window dump (env SVG_REF_FRAGILE=<file>; run the aligner with -T 1, so that the calls
+ * come in do_voting's (block, read, strand, end) order and the state below has one writer).
+ * Compiled into subjunc-dump only (-DSVG_HOOK_FRAGILE and its four --wrap flags, oracle/Makefile).
+ * Passive unless the variable is set.  One record per window of every
+ * core_fragile_junction_voting call (core-junction.c:5151-5422; the call, core.c:3141):
+ *   svg_ref_fwin (96 B), then n_used x svg_ref_fslot (28 B): every used slot of the finished vote
+ *   table in row-major order, as select_best_vote (sorted-hashtable.c:1128; the call,
+ *   core-junction.c:5346) receives it.
+ * start / length: the window's first genekey2int call (core-junction.c:5203, offset 0 of InBuff)
+ *   gives window_cursor as its distance from the read's first base; the NUL the reference puts at
+ *   InBuff[read_len] (core-junction.c:5188) gives read_len.
+ * junction / small_side: search_event (core-indel.c:1420) with the junction types is called here
+ *   exactly when core13_test_donor accepted (core-junction.c:5376), with pos_small.
+ * large_side / event_negative: from the junction event with that small side which the call
+ *   created or whose supporting_reads grew (the thread's event table before and after the call);
+ *   0xffffffff / 0xff when the call touched two such events.
+ */
+typedef struct {
+	unsigned int call;
+	unsigned short window, full_rl;
+	unsigned char negative_strand, junction, event_negative, pad;
+	unsigned int low_border, high_border, small_side, large_side;
+	short max_vote;
+	unsigned short n_used, start, length;
+	unsigned short items[GENE_VOTE_TABLE_SIZE];
+} svg_ref_fwin;
+typedef struct {
+	unsigned int pos;
+	short votes, coverage_start, coverage_end, rec[9];
+} svg_ref_fslot;
+
+#define FR_MAXW (MAX_READ_LENGTH / 60 + 2)
+static struct {
+	int inside, nwin, open;
+	unsigned int calls;
+	char *read;
+	int cursor, length;
+	svg_ref_fwin win[FR_MAXW];
+	svg_ref_fslot slot[FR_MAXW][GENE_VOTE_TABLE_SIZE * GENE_VOTE_SPACE];
+} fr;
+
+void __real_core_fragile_junction_voting(global_context_t *gc, thread_context_t *tc, char *rname, char *read, char *qual,
+                                         unsigned int full_rl, int negative_strand, int color_space,
+                                         unsigned int low_border, unsigned int high_border, gene_vote_t *vote);
+void __real_select_best_vote(gene_vote_t *vote);
+int __real_search_event(global_context_t *gc, HashTable *event_table, chromosome_event_t *event_space, unsigned int pos,
+                        int search_type, unsigned char event_type, chromosome_event_t **return_buffer);
+int __real_genekey2int(char *key, int space_type);
+
+int __wrap_genekey2int(char *key, int space_type)
+{
+	if (fr.inside && !fr.open) {
+		fr.open = 1;
+		fr.cursor = (int)(key - fr.read);
+		fr.length = (int)strlen(key);
+	}
+	return __real_genekey2int(key, space_type);
+}
+
+void __wrap_select_best_vote(gene_vote_t *vote)
+{
+	if (fr.inside && fr.nwin < FR_MAXW) {
+		svg_ref_fwin *w = &fr.win[fr.nwin];
+		svg_ref_fslot *s = fr.slot[fr.nwin];
+		int i, j, k, n = 0;
+		w->window = (unsigned short)fr.nwin;
+		w->max_vote = vote->max_vote;
+		w->start = (unsigned short)fr.cursor;
+		w->length = (unsigned short)fr.length;
+		for (i = 0; i < GENE_VOTE_TABLE_SIZE; i++) {
+			w->items[i] = vote->items[i];
+			for (j = 0; j < vote->items[i]; j++, n++) {
+				s[n].pos = vote->pos[i][j];
+				s[n].votes = vote->votes[i][j];
+				s[n].coverage_start = vote->coverage_start[i][j];
+				s[n].coverage_end = vote->coverage_end[i][j];
+				for (k = 0; k < 9; k++) s[n].rec[k] = vote->indel_recorder[i][j][k];
+			}
+		}
+		w->n_used = (unsigned short)n;
+		fr.nwin++;
+		fr.open = 0;
+	}
+	__real_select_best_vote(vote);
+}
+
+int __wrap_search_event(global_context_t *gc, HashTable *event_table, chromosome_event_t *event_space, unsigned int pos,
+                        int search_type, unsigned char event_type, chromosome_event_t **return_buffer)
+{
+	if (fr.inside && fr.nwin && search_type == EVENT_SEARCH_BY_SMALL_SIDE &&
+	    event_type == (CHRO_EVENT_TYPE_JUNCTION | CHRO_EVENT_TYPE_FUSION)) {
+		fr.win[fr.nwin - 1].junction = 1;
+		fr.win[fr.nwin - 1].small_side = pos;
+	}
+	return __real_search_event(gc, event_table, event_space, pos, search_type, event_type, return_buffer);
+}
+
+static void fr_events(global_context_t *gc, thread_context_t *tc, chromosome_event_t **space, unsigned int *n)
+{
+	if (tc) {
+		indel_thread_context_t *c = (indel_thread_context_t *)tc->module_thread_contexts[MODULE_INDEL_ID];
+		*space = c->event_space_dynamic; *n = c->total_events;
+	} else {
+		indel_context_t *c = (indel_context_t *)gc->module_contexts[MODULE_INDEL_ID];
+		*space = c->event_space_dynamic; *n = c->total_events;
+	}
+}
+
+void __wrap_core_fragile_junction_voting(global_context_t *gc, thread_context_t *tc, char *rname, char *read, char *qual,
+                                         unsigned int full_rl, int negative_strand, int color_space,
+                                         unsigned int low_border, unsigned int high_border, gene_vote_t *vote)
+{
+	static const char *fn;
+	static int fn_read;
+	if (!fn_read) { fn = getenv("SVG_REF_FRAGILE"); fn_read = 1; }
+	if (!fn || !fn[0]) {
+		__real_core_fragile_junction_voting(gc, tc, rname, read, qual, full_rl, negative_strand, color_space,
+		                                    low_border, high_border, vote);
+		return;
+	}
+	chromosome_event_t *es;
+	unsigned int n0, n1, i;
+	int w;
+	fr_events(gc, tc, &es, &n0);
+	unsigned short *before = (unsigned short *)malloc(sizeof(unsigned short) * (n0 + 1));
+	if (!before) { fprintf(stderr, "ref_dump_hook: out of memory (SVG_REF_FRAGILE)\n"); exit(1); }
+	for (i = 0; i < n0; i++) before[i] = es[i].supporting_reads;
+	memset(fr.win, 0, sizeof fr.win);
+	fr.nwin = 0; fr.open = 0; fr.read = read; fr.inside = 1;
+	__real_core_fragile_junction_voting(gc, tc, rname, read, qual, full_rl, negative_strand, color_space,
+	                                    low_border, high_border, vote);
+	fr.inside = 0;
+	fr_events(gc, tc, &es, &n1);
+	FILE *fp = fopen(fn, "ab");
+	for (w = 0; w < fr.nwin; w++) {
+		svg_ref_fwin *W = &fr.win[w];
+		W->call = fr.calls;
+		W->full_rl = (unsigned short)full_rl;
+		W->negative_strand = (unsigned char)negative_strand;
+		W->low_border = low_border; W->high_border = high_border;
+		if (W->junction) {
+			int hits = 0;
+			W->large_side = 0xffffffffu; W->event_negative = 0xff;
+			for (i = 0; i < n1; i++)
+				if (es[i].event_type == CHRO_EVENT_TYPE_JUNCTION && es[i].event_small_side == W->small_side &&
+				    (i >= n0 || es[i].supporting_reads != before[i])) {
+					hits++;
+					W->large_side = es[i].event_large_side;
+					W->event_negative = (unsigned char)es[i].is_negative_strand;
+				}
+			if (hits != 1) { W->large_side = 0xffffffffu; W->event_negative = 0xff; }
+		}
+		if (fp) {
+			fwrite(W, sizeof *W, 1, fp);
+			fwrite(fr.slot[w], sizeof(svg_ref_fslot), W->n_used, fp);
+		}
+	}
+	if (fp) fclose(fp);
+	free(before);
+	fr.calls++;
+}
+#endif /* SVG_HOOK_FRAGILE */

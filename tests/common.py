@@ -343,7 +343,230 @@ def vtedge_sj_reads(per, seed, lengths=(100, 200)):
     return _vt_finish(rng, rows, False)
 
 
-CUSTOM_GENOMES = {"lrrow54": lrrow54_genome, "vtedge": vtedge_genome}
+# ---- fredge: a genome built to reach the edges of fragile junction voting's vote table
+# (core_fragile_junction_voting, core-junction.c:5151-5422: per ~60-base window one gene_vote_t of
+# 30 rows x 24 slots filled by gehash_go_q, sorted-hashtable.c:750-927) for subjunc reads over 160
+# bases.  Constructs, FREDGE_GAP of i.i.d. sequence apart:
+#   edge_first / edge_last  150-bp-unit arrays of 30 / 12 copies flush against the genome's first and
+#              last base (12 never fill a row, so what the high border drops there is visible)
+#   t150_<n>   n = 23, 24, 25, 40 copies of a 150-bp unit: every copy's candidate in one row; 24
+#              fill it, the 25th is dropped
+#   r155_80    80 copies of a 155-bp unit: one row further per copy, more than 64 used slots
+#   f3rows     24 copies of a 150-bp unit that starts with 44 bases of a period-7 microsatellite
+#              (then random filler): a 16-mer of it recurs at shifts 0, 7, 14, 21 in every unit (96
+#              times in all: under the builder's repeat threshold of 100; the one 16-mer with a
+#              fifth shift is over it on a full index), 7 > the tolerance of 5 apart, so each shift
+#              fills a row of its own to 24, and where the first position is 0 or 3 mod 5 three of
+#              the rows are adjacent -- a candidate in the middle one scans 72 slots
+FREDGE_CONTIGS = [110000, 90000, 70000]
+FREDGE_SEED = 6161
+FREDGE_GAP = 2000
+FREDGE_T150 = (23, 24, 25, 40)
+FREDGE_EDGE_COPIES = 30
+FREDGE_EDGE_LAST_COPIES = 12
+FREDGE_F3_COPIES = 24
+FREDGE_F3_MS = 44
+FREDGE_LENGTHS = (161, 179, 180, 181, 239, 240, 241, 700, 1209)
+_fredge_cache = []
+
+
+def fredge_layout():
+    """-> (Genome, constructs), as vtedge_layout"""
+    if _fredge_cache:
+        return _fredge_cache[0]
+    from subread_amd.sim import Genome, random_genome
+    g = random_genome(FREDGE_CONTIGS, FREDGE_SEED)
+    seqs = [s.copy() for s in g.seqs]
+    rng = np.random.default_rng(FREDGE_SEED)
+
+    def unit150():
+        return _ACGT[rng.integers(0, 4, 150)]
+
+    bodies = [("edge_first", np.tile(unit150(), FREDGE_EDGE_COPIES), 150, FREDGE_EDGE_COPIES)]
+    bodies += [("t150_%d" % n, np.tile(unit150(), n), 150, n) for n in FREDGE_T150]
+    bodies += [("r155_80", np.tile(_ACGT[rng.integers(0, 4, 155)], 80), 155, 80)]
+    while True:
+        ms = _ACGT[rng.integers(0, 4, 7)]
+        if len(set(ms.tolist())) >= 3:
+            break
+    u = np.concatenate([np.tile(ms, 9)[:FREDGE_F3_MS], _ACGT[rng.integers(0, 4, 150 - FREDGE_F3_MS)]])
+    bodies += [("f3rows", np.tile(u, FREDGE_F3_COPIES), 150, FREDGE_F3_COPIES)]
+    cons = {}
+    ctg, cur = 0, 0
+    for name, body, ulen, copies in bodies:
+        if cur + len(body) + FREDGE_GAP > len(seqs[ctg]) - 20000:   # the contig's second half stays unique
+            ctg, cur = ctg + 1, FREDGE_GAP
+        seqs[ctg][cur:cur + len(body)] = body
+        cons[name] = dict(contig=ctg, start=cur, unit=ulen, copies=copies, length=len(body))
+        cur += len(body) + FREDGE_GAP
+    last = len(seqs) - 1
+    body = np.tile(unit150(), FREDGE_EDGE_LAST_COPIES)
+    seqs[last][len(seqs[last]) - len(body):] = body
+    cons["edge_last"] = dict(contig=last, start=len(seqs[last]) - len(body), unit=150, copies=FREDGE_EDGE_LAST_COPIES,
+                             length=len(body))
+    g = Genome(g.names, seqs)
+    for c in cons.values():
+        c["flat"] = int(g.starts[c["contig"]]) + c["start"]
+    _fredge_cache.append((g, cons))
+    return _fredge_cache[0]
+
+
+def fredge_genome():
+    return fredge_layout()[0]
+
+
+# the -F -M 1 index of fredge has two blocks: the second one's first base is chr3's first base, and
+# the first block runs FREDGE_BLOCK0_OVER bases into chr3 (index positions 0..207244 and 206018..)
+FREDGE_BLOCK0_OVER = 1226
+FREDGE_CHARS = ("n", "lower", "iupac", "u")
+
+
+def _fr_indel(rng, seg, L):
+    """one 1-3 base indel at least 20 bases from either end; seg holds L + 3 bases"""
+    r = bytearray(np.asarray(seg, np.uint8).tobytes())
+    at = int(rng.integers(20, L - 20))
+    k = int(rng.integers(1, 4))
+    if rng.random() < 0.5:
+        r[at:at] = _ACGT[rng.integers(0, 4, k)].tobytes()
+    else:
+        del r[at:at + k]
+    return np.frombuffer(bytes(r[:L]), np.uint8).copy()
+
+
+def _fr_chars(rng, src, kind):
+    a = np.asarray(src, np.uint8).copy()
+    L = len(a)
+    if kind == "n":
+        a[rng.integers(0, L, max(2, L // 60))] = ord("N")
+    elif kind == "lower":
+        s = int(rng.integers(0, L - 100))
+        a[s:s + 100] |= 0x20
+    elif kind == "iupac":
+        pos = rng.integers(0, L, max(2, L // 60))
+        a[pos] = np.frombuffer(b"RYKMSWBDHV.", np.uint8)[rng.integers(0, 11, len(pos))]
+    else:
+        a[a == ord("T")] = ord("U")
+    return a
+
+
+def fredge_reads(per, seed, lengths=FREDGE_LENGTHS, paired=False):
+    """`per` reads of every class at every length, in a seeded random order (VtReads):
+      in_<c>     exact reads inside construct c
+      id_<c>     the same with one 1-3 base indel
+      sj_<c>     spliced, GT...AG, intron 60..20000: one exon inside c, the other in unique sequence
+      ov_first / ov_last / ov_s<k> / ov_e<k>   20 random bases hanging over the genome's start and
+                 end and over the start / end of contig k
+      hi_last    exact reads that end 60..100 bases before the genome's end: on and past the high
+                 border (block end - read length - window length)
+      blk1 / blkhigh   exact reads of chr3 starting 0..7 bases in (the second block's first base
+                 and low border in the -F -M 1 index) and around FREDGE_BLOCK0_OVER - L - 60 (the
+                 first block's high border)
+      ch_<kind>  exact reads (half of them inside t150_25, the others in unique sequence of chr2) with
+                 N / a lowercase run / IUPAC codes and '.' / U for T
+    Every class alternates between the two strands from a random start, the ch_ classes through all
+    four combinations of strand and place.
+    paired: every read gets a mate -- the reverse complement of an exact read 300..600 bases
+    further on (-S fr), as long as the next length of `lengths` (the two ends differ in length when
+    `lengths` has more than one) -- and the reverse-strand pairs are swapped, the class's read being
+    r2: half the pairs of every class."""
+    g, cons = fredge_layout()
+    rng = np.random.default_rng(seed)
+    f = g.flat
+    G = len(f)
+    ag_end = np.flatnonzero((f[:-1] == ord("A")) & (f[1:] == ord("G"))).astype(np.int64) + 2
+    spans = sorted((c["flat"], c["flat"] + c["length"]) for c in cons.values())
+    rows = []
+
+    seen = {}       # class -> [emits so far, a random two bits: the class's first strand and place]
+
+    def turn(cls, step=1):
+        """the class's emit counter: its strand alternates from a random start, so every class has
+        both strands (and, paired, both orders of the pair) whatever else is emitted between"""
+        t = seen.setdefault(cls, [0, int(rng.integers(0, 4))])
+        t[0] += step
+        return t[0] - step + t[1]
+
+    def emit(src, cls, exact, at):
+        src = np.asarray(src, np.uint8)
+        st = turn(cls) % 2
+        mate = None
+        if paired:
+            m = min(max(at, 0) + int(rng.integers(300, 601)), G - mate_len)
+            mate = revcomp_bytes(f[m:m + mate_len])
+        if st:
+            rows.append((revcomp_bytes(src), mate, cls, exact, 1) if not paired else (mate, src, cls, exact, 1))
+        else:
+            rows.append((src, mate, cls, exact, 0))
+
+    def rnd(n):
+        return _ACGT[rng.integers(0, 4, n)]
+
+    for li, L in enumerate(lengths):
+        mate_len = lengths[(li + 1) % len(lengths)]
+        for _ in range(per):
+            for name, c in cons.items():
+                s = c["flat"] + int(rng.integers(0, c["length"] - L - 3)) if c["length"] > L + 3 else c["flat"]
+                s = min(s, G - L - 3)
+                emit(f[s:s + L], "in_" + name, True, s)
+                emit(_fr_indel(rng, f[s:s + L + 3], L), "id_" + name, False, s)
+            for name, c in cons.items():
+                if name == "edge_last":
+                    continue
+                seg = f[c["flat"]:c["flat"] + c["length"]]
+                gt = c["flat"] + np.flatnonzero((seg[:-1] == ord("G")) & (seg[1:] == ord("T")))
+                cend = int(g.starts[c["contig"]]) + int(g.lens[c["contig"]])
+                while True:
+                    a = int(rng.integers(30, L - 29))
+                    x = int(gt[rng.integers(0, len(gt))])
+                    if x - a < c["flat"]:
+                        continue
+                    d = int(np.exp(rng.uniform(np.log(60), np.log(20000))))
+                    k = int(np.searchsorted(ag_end, max(x + d, c["flat"] + c["length"] + 60)))
+                    if k >= len(ag_end):
+                        continue
+                    y = int(ag_end[k])
+                    if y - x - 2 > 20000 or y + (L - a) > cend or any(s0 < y + (L - a) and y < e0 for s0, e0 in spans):
+                        continue
+                    emit(np.concatenate([f[x - a:x], f[y:y + L - a]]), "sj_" + name, False, x - a)
+                    break
+            emit(np.concatenate([rnd(20), f[:L - 20]]), "ov_first", False, 0)
+            emit(np.concatenate([f[G - (L - 20):], rnd(20)]), "ov_last", False, G - L)
+            for k in (1, 2):
+                s0 = int(g.starts[k])
+                emit(np.concatenate([rnd(20), f[s0:s0 + L - 20]]), "ov_s%d" % (k + 1), False, s0)
+                emit(np.concatenate([f[s0 - (L - 20):s0], rnd(20)]), "ov_e%d" % k, False, s0 - L)
+            s = G - L - int(rng.integers(60, 101))
+            emit(f[s:s + L], "hi_last", True, s)
+            s = int(g.starts[2]) + int(rng.integers(0, 8))
+            emit(f[s:s + L], "blk1", True, s)
+            s = int(g.starts[2]) + max(0, FREDGE_BLOCK0_OVER - L - 60 + int(rng.integers(-30, 31)))
+            emit(f[s:s + L], "blkhigh", True, s)
+            for kind in FREDGE_CHARS:
+                c = cons["t150_25"]
+                if (turn("ch_" + kind, 0) >> 1) & 1:    # the place changes every second emit, the strand every one
+                    s = c["flat"] + int(rng.integers(0, max(1, c["length"] - L)))
+                else:
+                    s = int(g.starts[1]) + 60000 + int(rng.integers(0, 20000))
+                emit(_fr_chars(rng, f[s:s + L], kind), "ch_" + kind, False, s)
+    return _vt_finish(rng, rows, paired)
+
+
+def fredge_retry_reads(n=640, seed=99):
+    """161-base reads of the exactly-24-copy array with one small indel each: 6 windows per read
+    with up to 24 tied top slots, all of them reported -- more reported slots than
+    svg_fragile_batch's first slot buffer (2 * windows + 1024) holds, so its retry runs"""
+    g, cons = fredge_layout()
+    rng = np.random.default_rng(seed)
+    c = cons["t150_24"]
+    out = []
+    for i in range(n):
+        s = c["flat"] + int(rng.integers(0, c["length"] - 165))
+        r = _fr_indel(rng, g.flat[s:s + 164], 161)
+        out.append(revcomp_bytes(r).tobytes() if i % 2 else r.tobytes())
+    return ReadBatch.from_list(out)
+
+
+CUSTOM_GENOMES = {"lrrow54": lrrow54_genome, "vtedge": vtedge_genome, "fredge": fredge_genome}
 
 
 def synth_genome(gname):

@@ -67,9 +67,10 @@ def hbm_builds(index_cache):
 
 
 def test_fixture_keys():
-    assert MB_KEYS == sorted(["synth4242_fullM1", "synth4242_gappedM1", "long777_fullM17", "long777_gappedM6", "vtedge_fullM1"])
+    assert MB_KEYS == sorted(["synth4242_fullM1", "synth4242_gappedM1", "long777_fullM17", "long777_gappedM6", "vtedge_fullM1",
+                              "fredge_fullM1"])
     assert [fixture_blocks(k) for k in ("synth4242_fullM1", "synth4242_gappedM1", "long777_fullM17", "long777_gappedM6",
-                                        "vtedge_fullM1")] == [4, 2, 6, 4, 2]
+                                        "vtedge_fullM1", "fredge_fullM1")] == [4, 2, 6, 4, 2, 2]
 
 
 @pytest.mark.parametrize("key", MB_KEYS)
