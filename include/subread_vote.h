@@ -335,6 +335,116 @@ int  svg_cell_vote_batch(svg_index *idx, const svg_cell_params *p, const svg_pac
 void svg_cell_vote_free(svg_cell_votes *res);
 
 /*
+ * cellCounts' voting step and, behind it on the GPU, everything that
+ * cellCounts_select_and_write_alignments does (cell-counts.c:2648-2719) up to, but not including,
+ * its calls of cellCounts_write_read_in_batch_bin: the choice of at most max_voting_simples slots
+ * of the table (:2654-2686, cellCounts_update_top_three :2296-2310), cellCounts_explain_one_read
+ * for each (:2520-2627: cellCounts_indel_recorder_copy :2352-2424, cellCounts_find_soft_clipping
+ * :326-396, cellCounts_meet_in_the_middle :2462-2506, cellCounts_matchBin_chro :2426-2458,
+ * find_subread_end input-files.c:1371-1377, cellCounts_reduce_Cigar :238-265,
+ * cellCounts_calculate_pos_weight :1535-1571, cellCounts_test_score :2508-2511), the quick_sort
+ * of the scores (:2691-2698; core.c:4690-4714, unstable: ties come out in its order) and the
+ * choice of the records to write (:2700-2716).  The vote tables stay on the device.
+ *
+ * Per read (batch order) one svg_cell_aln_head: reporting_multi_alignment_no after its min with
+ * max_reported_alignments_per_read, the number of its records and the index of the first; no
+ * records = the reference writes the read as unmapped.  Per call of the writer with a
+ * reporting_index >= 0, in the order of the calls, one svg_cell_aln: reporting_positions (0-based
+ * linear, before the writer's + 1 and locate_gene_position), reporting_flags (0 or 16),
+ * reporting_mapq, reporting_editing_distance, reporting_scores and the reduced CIGAR as text.
+ * locate_gene_position ("no chromosome: unmapped"), the feature lookup and the writers stay with
+ * the caller.
+ *
+ * The CIGAR field.  A record is written for a score > 0 only, i.e. rebuilt_rlen == read_len <= 160:
+ * the counts of the text's M, S and I pieces are positive and sum to at most 160.  The table slot
+ * has at most 7 sections (toli <= 21), so explain_one_read appends at most 6 pieces
+ * "%dM%dM%d%c%dM" between the head "%dS" and the tail "%dM" "%dS".  Of a piece's numbers only
+ * the second and fourth can be negative ('-' is an operation of count 1 to reduce_Cigar: "1-"),
+ * as can the tail's M.  After the merge of equal neighbours that leaves at most 22 M/S/I pieces
+ * (S, 3 M + I, 5 x (2 M + I), M, S), 13 "1-" and 6 D of one digit (|indel| < 5; merged ones are
+ * fewer pieces).  22 positive counts that sum to <= 160 have at most 37 digits (at most 15 of
+ * them reach 10), so the text has at most 22 + 37 + 26 + 12 = 97 characters: SVG_CELL_CIGAR = 108
+ * holds it with its NUL and rounds the record to 128 bytes.
+ *
+ * Parameters (svg_cell_align_params_default: the defaults of cell-counts.c:517-529; ranges: the
+ * clamps of :538-569; outside them SVG_E_ARG):
+ *   total_subreads                         7..20, default 10
+ *   max_indel_length                       5
+ *   min_votes_per_mapped_read              1..64, default 3
+ *   max_differential_from_top_vote_number  1..30, default 2
+ *   max_mismatching_bases_in_reads         0..100, default 3
+ *   min_mapped_length_for_mapped_read      -1..160, default 40
+ *   max_reported_alignments_per_read       1..30, default 1
+ * max_voting_simples is max(3, max_reported_alignments_per_read) (:518, :604) and
+ * max_distinct_top_vote_numbers 3 (:522).  A multi-block index is SVG_E_UNSUPPORTED.
+ *
+ * The exon weight (:1535-1571) is read from two bit planes, exon bases and exon bases with 100
+ * bases of flank, that svg_cell_set_exons fills from inclusive linear intervals as :938-959 fill
+ * exonic_region_bitmap: an interval with an end above 0xffffff00 sets nothing (:941), and the
+ * flank loop starts at the unsigned start - 100, so an exon that starts below 100 gets no flank
+ * bits at all.  The planes cover the linear positions below the end of the .array image plus
+ * SVG_CELL_EXON_TAIL; a bit beyond them is not set and reads as 0.  A later call replaces the
+ * list; n = 0 clears it.  With no exons set every weight is 10.
+ *
+ * Outside the reference's contract, and memory-safe here:
+ *   - cellCounts_get_index_int has no bounds check.  Where a candidate's soft-clip scan or
+ *     meet-in-the-middle asks for a genome base outside the .array image the reference's answer
+ *     is undefined; this library reads such a base as code 0.  (matchBin_chro checks, and returns
+ *     0, in the reference too.)
+ *   - a read with one subread per strand (16 .. 16 + gap bases): find_subread_end divides by zero
+ *     in the reference as soon as a slot is explained; here such a read has a zero head.
+ *   - a slot whose recorder copies to 7 sections makes indel_recorder_copy write one element past
+ *     its array (:2402); here the write is dropped.
+ * A candidate with a score > 0 whose text does not fit SVG_CELL_CIGAR (the bound above says there
+ * is none) is counted on the device and fails the call with SVG_E_DEVICE.
+ * With svg_set_timing on, svg_cell_align_timing returns, and resets, the milliseconds (HIP events
+ * around each launch) summed per kernel since the last call: probe, tally, select, explain, emit,
+ * scan + compact.
+ */
+#define SVG_CELL_CIGAR       108
+#define SVG_CELL_EXON_TAIL   512
+#define SVG_CELL_MAX_REPORT  30     /* SCRNA_HIGHEST_REPORTED_ALIGNMENTS */
+
+typedef struct svg_cell_align_params {
+	int32_t total_subreads;
+	int32_t max_indel_length;
+	int32_t min_votes_per_mapped_read;
+	int32_t max_differential_from_top_vote_number;
+	int32_t max_mismatching_bases_in_reads;
+	int32_t min_mapped_length_for_mapped_read;
+	int32_t max_reported_alignments_per_read;
+} svg_cell_align_params;
+
+typedef struct svg_cell_aln_head {
+	uint64_t first_record;            /* the read's first record in alns (0 where it has none) */
+	uint16_t n_records;
+	uint16_t multi_alignment_no;      /* reporting_multi_alignment_no */
+	uint32_t _pad;
+} svg_cell_aln_head;                  /* 16 bytes */
+
+typedef struct svg_cell_aln {
+	int64_t  score;                   /* reporting_scores */
+	uint32_t position;                /* reporting_positions */
+	int16_t  flags;                   /* reporting_flags: 0, or 16 */
+	int16_t  mapq;                    /* reporting_mapq */
+	int32_t  editing_distance;        /* reporting_editing_distance */
+	char     cigar[SVG_CELL_CIGAR];   /* reporting_cigars, NUL-terminated, zero to the end */
+} svg_cell_aln;                       /* 128 bytes */
+
+typedef struct svg_cell_alns {
+	uint64_t n_reads, n_records;
+	svg_cell_aln_head *heads;         /* one per read, batch order */
+	svg_cell_aln *alns;               /* read by read, in the order of the writer's calls */
+} svg_cell_alns;
+
+void svg_cell_align_params_default(svg_cell_align_params *p);
+int  svg_cell_set_exons(svg_index *idx, const uint32_t *starts, const uint32_t *stops, uint64_t n);
+int  svg_cell_align_batch(svg_index *idx, const svg_cell_align_params *p, const svg_packed_reads *reads,
+                          svg_cell_alns *res);
+void svg_cell_align_free(svg_cell_alns *res);
+int  svg_cell_align_timing(svg_index *idx, double ms[6]);
+
+/*
  * Fragile junction voting of subjunc reads longer than 160 bases (core_fragile_junction_voting,
  * core-junction.c:5151-5422; do_voting runs it for every index block, strand and read end,
  * core.c:3138-3142).  The read (strand 0: as fetched after the -S reversal, strand 1: its

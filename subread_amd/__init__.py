@@ -34,6 +34,8 @@ EXPORTS = [
     "svg_vote_batch_packed_device", "svg_probe_keys", "svg_probe_keys_device", "svg_host_threads",
     "svg_fragile_batch", "svg_fragile_free", "svg_set_option", "svg_get_option",
     "svg_cell_vote_batch", "svg_cell_vote_free",
+    "svg_cell_align_params_default", "svg_cell_align_batch", "svg_cell_align_free", "svg_cell_set_exons",
+    "svg_cell_align_timing",
     "svg_host_placement", "svg_host_alloc", "svg_host_free", "svg_cpulist_parse",
     # sublong's voting step (include/subread_long.h)
     "svg_long_vote_batch", "svg_long_free",
@@ -149,6 +151,16 @@ def lib():
         L.svg_cell_vote_batch.argtypes = [vp] * 4
         L.svg_cell_vote_batch.restype = i32
         L.svg_cell_vote_free.argtypes = [vp]
+        if hasattr(L, "svg_cell_align_batch"):   # (as for svg_long_vote_batch below)
+            L.svg_cell_align_params_default.argtypes = [vp]
+            L.svg_cell_align_params_default.restype = None
+            L.svg_cell_align_batch.argtypes = [vp] * 4
+            L.svg_cell_align_batch.restype = i32
+            L.svg_cell_align_free.argtypes = [vp]
+            L.svg_cell_set_exons.argtypes = [vp, vp, vp, u64]
+            L.svg_cell_set_exons.restype = i32
+            L.svg_cell_align_timing.argtypes = [vp, vp]
+            L.svg_cell_align_timing.restype = i32
         if hasattr(L, "svg_long_vote_batch"):   # (older builds loaded side by side for A/B runs lack it)
             L.svg_long_vote_batch.argtypes = [vp] * 3
             L.svg_long_vote_batch.restype = i32
@@ -544,6 +556,46 @@ class VoteIndex:
             return res.arrays()
         finally:
             lib().svg_cell_vote_free(ctypes.byref(res))
+
+    def cell_align(self, packed_reads, **params):
+        """svg_cell_align_batch: the vote of cell_vote, then cellCounts_select_and_write_alignments
+        (cell-counts.c:2648-2719) up to its calls of the writer, for a PackedBatch -> (heads, alns):
+        one CELL_ALN_HEAD_DTYPE per read and one CELL_ALN_DTYPE per reported alignment, read i's at
+        alns[first_record : first_record + n_records].  params: the fields of svg_cell_align_params
+        (defaults: svg_cell_align_params_default)."""
+        from .abi import SvgCellAlignParams, SvgCellAlns
+        p = SvgCellAlignParams()
+        lib().svg_cell_align_params_default(ctypes.byref(p))
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("cell_align: no parameter %r" % k)
+            setattr(p, k, int(v))
+        s = packed_reads.struct()
+        res = SvgCellAlns()
+        rc = lib().svg_cell_align_batch(self.h, ctypes.byref(p), ctypes.byref(s), ctypes.byref(res))
+        _check(rc, "svg_cell_align_batch")
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_align_free(ctypes.byref(res))
+
+    def cell_align_timing(self):
+        """svg_cell_align_timing: ms per kernel (probe, tally, select, explain, emit, scan + compact)
+        summed over the cell_align calls since the last call, under set_timing(True)."""
+        ms = (ctypes.c_double * 6)()
+        _check(lib().svg_cell_align_timing(self.h, ms), "svg_cell_align_timing")
+        return dict(zip(("probe", "tally", "select", "explain", "emit", "scan_compact"), (float(x) for x in ms)))
+
+    def set_cell_exons(self, starts, stops):
+        """svg_cell_set_exons: the exon intervals (inclusive linear positions, as the reference gets
+        them from linear_gene_position) that cell_align's weights are read from; an empty list
+        clears them."""
+        a = np.ascontiguousarray(starts, dtype=np.uint32)
+        b = np.ascontiguousarray(stops, dtype=np.uint32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("set_cell_exons: starts and stops must be 1-d arrays of one length")
+        _check(lib().svg_cell_set_exons(self.h, a.ctypes.data, b.ctypes.data, ctypes.c_uint64(len(a))),
+               "svg_cell_set_exons")
 
     def long_vote(self, reads):
         """svg_long_vote_batch: sublong's voting step (LRMdo_one_voting_read + the copy and location

@@ -190,6 +190,41 @@ class SvgCellVotes(ctypes.Structure):
         return h, s
 
 
+# svg_cell_aln_head / svg_cell_aln (include/subread_vote.h): what svg_cell_align_batch returns per
+# read and per reported alignment (cellCounts_select_and_write_alignments, cell-counts.c:2648-2719)
+CELL_CIGAR = 108
+CELL_ALN_HEAD_DTYPE = np.dtype([("first_record", "<u8"), ("n_records", "<u2"), ("multi_alignment_no", "<u2"),
+                                ("_pad", "<u4")])
+CELL_ALN_DTYPE = np.dtype([("score", "<i8"), ("position", "<u4"), ("flags", "<i2"), ("mapq", "<i2"),
+                           ("editing_distance", "<i4"), ("cigar", "S%d" % CELL_CIGAR)])
+assert CELL_ALN_HEAD_DTYPE.itemsize == 16 and CELL_ALN_DTYPE.itemsize == 128
+
+
+class SvgCellAlignParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in
+                ("total_subreads", "max_indel_length", "min_votes_per_mapped_read",
+                 "max_differential_from_top_vote_number", "max_mismatching_bases_in_reads",
+                 "min_mapped_length_for_mapped_read", "max_reported_alignments_per_read")]
+
+
+assert ctypes.sizeof(SvgCellAlignParams) == 28
+
+
+class SvgCellAlns(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint64), ("n_records", ctypes.c_uint64),
+                ("heads", ctypes.c_void_p), ("alns", ctypes.c_void_p)]
+
+    def arrays(self):
+        """Copies of the heads and alignment records as numpy structured arrays."""
+        h = np.zeros(self.n_reads, dtype=CELL_ALN_HEAD_DTYPE)
+        a = np.zeros(self.n_records, dtype=CELL_ALN_DTYPE)
+        if self.n_reads:
+            ctypes.memmove(h.ctypes.data, self.heads, h.nbytes)
+        if self.n_records:
+            ctypes.memmove(a.ctypes.data, self.alns, a.nbytes)
+        return h, a
+
+
 # svg_long_vote (include/subread_long.h): one used slot of sublong's LRMgene_vote_t
 LONG_VOTE_DTYPE = np.dtype([("pos", "<u4"), ("coverage_start", "<u4"), ("coverage_end", "<u4"),
                             ("votes", "<u2"), ("negative", "u1"), ("_pad", "u1"), ("slot", "<u4")])

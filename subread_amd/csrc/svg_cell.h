@@ -1,0 +1,40 @@
+// svg_cell.h -- what svg_cell.hip (the cellCounts vote) shares with svg_cell_align.hip (the step
+// behind it): the kernels' parameter block and the launch of the probe and tally kernels.
+#ifndef SVG_CELL_H
+#define SVG_CELL_H
+#include "svg_device.h"
+#include "svg_keylookup.h"
+
+#define C_SUB   20                                 // SCRNA_SUBREADS_HARD_LIMIT, cell-counts.c:29
+#define C_SLOTS (SVG_CELL_ROWS * SVG_CELL_SPACE)   // 51
+#define C_PRIME 66889u                             // VOTING_PRIME_NUMBER, cell-counts.c:2749
+#define C_NEG   2048                               // IS_NEGATIVE_STRAND, subread.h:107
+#define C_STACK 8                                  // ranges the sort's stack has room for (it holds at most 5)
+
+struct CellParams {
+	KeyTable kt;
+	const uint32_t *vals;
+	int gap, total_subreads, max_indel;
+	// the chunk's reads: read r at base starts[r], or base0 + r * stride
+	const uint32_t *bases, *xmask;
+	const uint64_t *starts;
+	uint64_t stride, base0;
+	const uint16_t *lens;
+	uint32_t n;
+	uint2 *probes;             // [2 * C_SUB][n]
+	svg_cell_head *heads;      // [n]
+	svg_cell_slot *staging;    // [n][C_SLOTS]
+	svg_cell_slot *compact;
+	uint64_t slot_base;        // slots of the chunks before this one
+	uint64_t *total;           // the chunk's slot count
+};
+
+__device__ __forceinline__ uint64_t cell_read_base(const CellParams &cp, uint32_t r)
+{
+	return cp.starts ? cp.starts[r] : cp.base0 + (uint64_t)r * cp.stride;
+}
+
+// cell_probe_kernel and cell_tally_kernel for one chunk on st: heads (first_slot unset) and the
+// reads' 51 staging records each; mid (or NULL) is recorded between the two kernels
+void cell_launch_vote(const CellParams &cp, int img, int n_cu, hipStream_t st, hipEvent_t mid = NULL);
+#endif

@@ -25,30 +25,7 @@
 #include "svg_internal.h"
 #include "svg_device.h"
 #include "svg_keylookup.h"
-
-#define C_SUB   20                                 // SCRNA_SUBREADS_HARD_LIMIT, cell-counts.c:29
-#define C_SLOTS (SVG_CELL_ROWS * SVG_CELL_SPACE)   // 51
-#define C_PRIME 66889u                             // VOTING_PRIME_NUMBER, cell-counts.c:2749
-#define C_NEG   2048                               // IS_NEGATIVE_STRAND, subread.h:107
-#define C_STACK 8                                  // ranges the sort's stack has room for (it holds at most 5)
-
-struct CellParams {
-	KeyTable kt;
-	const uint32_t *vals;
-	int gap, total_subreads, max_indel;
-	// the chunk's reads: read r at base starts[r], or base0 + r * stride
-	const uint32_t *bases, *xmask;
-	const uint64_t *starts;
-	uint64_t stride, base0;
-	const uint16_t *lens;
-	uint32_t n;
-	uint2 *probes;             // [2 * C_SUB][n]
-	svg_cell_head *heads;      // [n]
-	svg_cell_slot *staging;    // [n][C_SLOTS]
-	svg_cell_slot *compact;
-	uint64_t slot_base;        // slots of the chunks before this one
-	uint64_t *total;           // the chunk's slot count
-};
+#include "svg_cell.h"
 
 // cellCounts' subread plan (cell-counts.c:3079-3082, C's truncating divisions): the step in
 // 1/65536 bases and the subreads per strand.  Lengths 16 .. 15 + gap have a span <= 0: the step
@@ -59,11 +36,6 @@ __device__ __forceinline__ int cell_plan(int len, int gap, int total, int &step)
 	step = span / (total - 1);
 	if (step < (gap << 16)) step = gap << 16;
 	return 1 + span / step;
-}
-
-__device__ __forceinline__ uint64_t cell_read_base(const CellParams &cp, uint32_t r)
-{
-	return cp.starts ? cp.starts[r] : cp.base0 + (uint64_t)r * cp.stride;
 }
 
 // the key (genekey2int) of the 16 bases at offset off of strand s of a read of len bases at
@@ -312,6 +284,18 @@ __global__ void __launch_bounds__(256) cell_compact_kernel(CellParams cp)
 	}
 }
 
+void cell_launch_vote(const CellParams &cp, int img, int n_cu, hipStream_t st, hipEvent_t mid)
+{
+	const uint64_t k = cp.n, bmax = (uint64_t)n_cu * 16;
+	uint64_t pblocks = (k * 2 * C_SUB + 255) / 256;
+	if (pblocks > bmax) pblocks = bmax;
+	if (img == KEYS_CODE) hipLaunchKernelGGL(cell_probe_kernel<KEYS_CODE>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
+	else if (img == KEYS_KHASH) hipLaunchKernelGGL(cell_probe_kernel<KEYS_KHASH>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
+	else hipLaunchKernelGGL(cell_probe_kernel<KEYS_LITERAL>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
+	if (mid) hipEventRecord(mid, st);
+	hipLaunchKernelGGL(cell_tally_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, cp);
+}
+
 extern "C" void svg_cell_vote_free(svg_cell_votes *res)
 {
 	if (!res) return;
@@ -403,14 +387,10 @@ extern "C" int svg_cell_vote_batch(svg_index *h, const svg_cell_params *p, const
 		cp.compact = (svg_cell_slot *)d[7];
 		cp.slot_base = nslots;
 		cp.total = (uint64_t *)d[8];
-		uint64_t pblocks = (k * 2 * C_SUB + 255) / 256, cblocks = (k * C_SLOTS + 255) / 256;
+		uint64_t cblocks = (k * C_SLOTS + 255) / 256;
 		const uint64_t bmax = (uint64_t)h->n_cu * 16;
-		if (pblocks > bmax) pblocks = bmax;
 		if (cblocks > bmax) cblocks = bmax;
-		if (img == KEYS_CODE) hipLaunchKernelGGL(cell_probe_kernel<KEYS_CODE>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
-		else if (img == KEYS_KHASH) hipLaunchKernelGGL(cell_probe_kernel<KEYS_KHASH>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
-		else hipLaunchKernelGGL(cell_probe_kernel<KEYS_LITERAL>, dim3((unsigned)pblocks), dim3(256), 0, st, cp);
-		hipLaunchKernelGGL(cell_tally_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, cp);
+		cell_launch_vote(cp, img, h->n_cu, st);
 		hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(1024), 0, st, cp);
 		hipLaunchKernelGGL(cell_compact_kernel, dim3((unsigned)cblocks), dim3(256), 0, st, cp);
 		uint64_t used = 0;

@@ -191,6 +191,10 @@ struct svg_index {
 	int stored;
 	// svg_long_vote_batch's grow-only device arenas and pinned staging (svg_long.hip)
 	struct svg_longws *lws;
+	// svg_cell_set_exons's two bit planes (svg_cell_align.hip); NULL: no exons
+	uint32_t *d_exons;
+	// svg_cell_align_batch under svg_set_timing: ms per kernel (probe, tally, select, explain, emit, scan + compact)
+	double cell_ms[6];
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { svg_set_error("HIP error %s at %s:%d", hipGetErrorString(_e), __FILE__, __LINE__); return SVG_E_DEVICE; } } while (0)

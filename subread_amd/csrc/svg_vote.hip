@@ -3171,7 +3171,7 @@ extern "C" void svg_index_close(svg_index *h)
 				if (h->tev[k][i][j]) hipEventDestroy(h->tev[k][i][j]);
 	hipFree(h->d_bstart); hipFree(h->d_keys); hipFree(h->d_vals); hipFree(h->d_values); hipFree(h->d_chr);
 	hipFree(h->d_bgrp); hipFree(h->d_keys8); hipFree(h->d_bline); hipFree(h->d_bcode); hipFree(h->d_khash); hipFree(h->d_ksorted);
-	hipFree(h->d_scratch); hipFree(h->d_stats); hipFree(h->d_err);
+	hipFree(h->d_scratch); hipFree(h->d_stats); hipFree(h->d_err); hipFree(h->d_exons);
 	if (h->ev_last) hipEventDestroy(h->ev_last);
 	streams_release(h);
 	svg_host_index_free(&h->host);
