@@ -445,6 +445,115 @@ void svg_cell_align_free(svg_cell_alns *res);
 int  svg_cell_align_timing(svg_index *idx, double ms[6]);
 
 /*
+ * The rest of what cellCounts computes per read before it only writes files: for every call of
+ * cellCounts_write_read_in_batch_bin that svg_cell_align_batch records, the gene assignment of
+ * the alignment (cell-counts.c:2061-2088, cellCounts_find_hits_for_mapped_section :1575-1654,
+ * cellCounts_summarize_entrez_hits :2039-2059), the multi-overlap rule (:1982) and, per read, the
+ * cell barcode (cellCounts_get_cellbarcode_no :1701-1768).  svg_cell_assign_batch returns what
+ * svg_cell_align_batch returns, in the same layout (res->alns), and beside it
+ *   hits[k]  for alns.alns[k]: the contig (index into the .reads table), or -1 where the reference
+ *            turns the call into an unmapped one (locate_gene_position(position + 1) leaves
+ *            chro_name NULL, gene-algorithms.c:441-511 with rl = 0: a position inside a contig's
+ *            leading padding, past the last base that lies 15 bases short of the next padding, or
+ *            beyond the last contig; chro_pos and nhits are then 0, as in the call of :2087);
+ *            chro_pos as cellCounts_vote_and_add_count gets it (after get_soft_clipping_length is
+ *            added, core.c:1232: the count of a head S only); nhits after the summary and after
+ *            the rule of :1982; first_gene, where its nhits gene numbers start in genes;
+ *   genes    the gene numbers in the reference's hits_indices order (first seen first);
+ *   cell_barcode_no  per read, the whitelist number or -1.
+ * svg_cell_assign_records runs the same assignment over records the caller holds in host memory.
+ *
+ * The walk follows the reference as written.  Every M section of the CIGAR text is looked up as
+ * [chro_pos, chro_pos + length], both ends inclusive: the cursor of :2073-2083 never advances
+ * (add_curs is computed and not added), and neither does it here.  A section starts at the
+ * reverse-table bucket min(begin / 131072, chro_possible_length / 131072), skips unset buckets up
+ * to min((1 + end) / 131072, chro_possible_length / 131072 + 1) (:1602-1609), walks the blocks
+ * from there to the contig's last (break on block_min_start > end, continue on block_max_end <
+ * begin) and the items of a block (stop >= begin, then break on start > end), and takes an item
+ * whose strand equals the record's flag 16.
+ *
+ * svg_cell_set_annotation takes the features in annotation-file order: the contig as an index
+ * into the handle's .reads table (the caller resolves names, the chr-prefix fallbacks of :897-906
+ * and :1581-1596 included, and leaves out a feature on no contig of the index), start and end
+ * 1-based inclusive as the annotation gives them, the strand (1 = '-') and the caller's gene
+ * number (the reference numbers genes by first appearance, :1163).  On the host it builds what
+ * cellCounts_sort_feature_info builds (:1099-1251): each contig's features by start under the
+ * reference's merge_sort (core.c:4736-4753: selection sort of runs of at most 11, and a merge
+ * that on equal starts takes the second run's item first, so ties are not in file order), the
+ * blocks with the sqrt-sized bins of :1180, the reverse tables, chro_possible_length (:1275: the
+ * difference of the .reads offsets, padding included; :920: raised to end + 1).  It also fills the
+ * two exon planes of svg_cell_set_exons from linear_gene_position of start and end (:939-940)
+ * through the same code.  A later call replaces everything, n = 0 clears the annotation and the
+ * planes.  allow_multi_overlap is allow_multi_overlapping_reads.  SVG_E_ARG: a contig index out
+ * of range, start > end (the reference's assert of :984), a strand above 1, and a feature whose
+ * (end + 1) / 131072 + 2 exceeds the (length + 1 Mbase) / 131072 + 2 buckets that the reference
+ * allocates for its contig's reverse table (:1277-1278) and writes without a check (:935, :1181).
+ *
+ * svg_cell_set_barcodes takes the whitelist as n strings of `length` characters: 2..16, A/C/G/T
+ * only, distinct; anything else is SVG_E_ARG with the reason in svg_last_error.  n = 0 clears it.
+ * The device image is the barcodes as 2-bit codes in whitelist order and the two half-key lists of
+ * cellCounts_make_barcode_HT_table (:272-304; F: even positions, S: odd ones, length / 2
+ * characters each) as direct-indexed CSR rows of 4 ^ (length / 2) keys, each row in ascending
+ * whitelist order.  There is no third table for the exact probe: a barcode equal to a whitelist
+ * entry has its F key, so the F row answers it.  The reference's order holds: the exact entry
+ * wins wherever it stands; else the first entry of the F row, then of the S row, whose
+ * hamming_dist_ATGC_max2 (input-blc.c:1109-1120) is exactly 1 (an entry of both rows was tested
+ * in the F row already, so skipping it in the S row, as :1738-1745 do, changes nothing).
+ * Read barcodes come as a second svg_packed_reads of the same count, `length` bases each.  An
+ * exception bit stands for 'N': is_ATGC (input-blc.c:1054) accepts N, so the comparison goes on
+ * past it and the N counts as one mismatch; a half key with an N matches no row.  Any other
+ * character, at which hamming_dist_ATGC_max2 would stop, is outside this contract.
+ * barcodes = NULL or no whitelist: cell_barcode_no -1 for every read.  No annotation: nhits 0
+ * everywhere, contig and chro_pos still filled.
+ *
+ * Bound: a record holds at most SVG_CELL_MAX_GENES distinct genes.  With allow_multi_overlap 0
+ * the bound cannot be met (two genes already make nhits 0); with it set, an alignment over more
+ * distinct genes is counted on the device and fails the call with SVG_E_DEVICE, never truncated.
+ * Outside the reference's contract: an alignment over more than MAX_HIT_NUMBER (10^6) features
+ * stops the reference's section scan with an error message; here the scan goes on.
+ * svg_cell_assign_timing (under svg_set_timing) returns and resets the summed milliseconds of
+ * the assign kernel, the barcode kernel and the gene scan + compact.
+ */
+#define SVG_CELL_MAX_GENES 16
+
+typedef struct svg_cell_feature {
+	uint32_t contig;                  /* index into the .reads table */
+	uint32_t start, end;              /* 1-based, inclusive */
+	int32_t  gene;
+	uint8_t  is_negative_strand;
+	uint8_t  _pad[3];
+} svg_cell_feature;                   /* 20 bytes */
+
+typedef struct svg_cell_hit {
+	int32_t  contig;                  /* -1: written as unmapped */
+	int32_t  chro_pos;
+	uint32_t nhits;
+	uint32_t _pad;
+	uint64_t first_gene;              /* genes[first_gene .. first_gene + nhits) (0 where nhits is 0) */
+} svg_cell_hit;                       /* 24 bytes */
+
+typedef struct svg_cell_hits {
+	uint64_t n_records, n_genes;
+	svg_cell_hit *hits;               /* one per svg_cell_aln */
+	int32_t *genes;
+} svg_cell_hits;
+
+typedef struct svg_cell_assigned {
+	svg_cell_alns alns;               /* as svg_cell_align_batch returns it */
+	svg_cell_hits hits;
+	int32_t *cell_barcode_no;         /* one per read */
+} svg_cell_assigned;
+
+int  svg_cell_set_annotation(svg_index *idx, const svg_cell_feature *features, uint64_t n, int allow_multi_overlap);
+int  svg_cell_set_barcodes(svg_index *idx, const char *const *barcodes, uint64_t n, int length);
+int  svg_cell_assign_batch(svg_index *idx, const svg_cell_align_params *p, const svg_packed_reads *reads,
+                           const svg_packed_reads *barcodes, svg_cell_assigned *res);
+void svg_cell_assign_free(svg_cell_assigned *res);
+int  svg_cell_assign_records(svg_index *idx, const svg_cell_aln *alns, uint64_t n, svg_cell_hits *hits);
+void svg_cell_hits_free(svg_cell_hits *hits);
+int  svg_cell_assign_timing(svg_index *idx, double ms[3]);
+
+/*
  * Fragile junction voting of subjunc reads longer than 160 bases (core_fragile_junction_voting,
  * core-junction.c:5151-5422; do_voting runs it for every index block, strand and read end,
  * core.c:3138-3142).  The read (strand 0: as fetched after the -S reversal, strand 1: its

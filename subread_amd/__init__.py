@@ -36,6 +36,8 @@ EXPORTS = [
     "svg_cell_vote_batch", "svg_cell_vote_free",
     "svg_cell_align_params_default", "svg_cell_align_batch", "svg_cell_align_free", "svg_cell_set_exons",
     "svg_cell_align_timing",
+    "svg_cell_set_annotation", "svg_cell_set_barcodes", "svg_cell_assign_batch", "svg_cell_assign_free",
+    "svg_cell_assign_records", "svg_cell_hits_free", "svg_cell_assign_timing",
     "svg_host_placement", "svg_host_alloc", "svg_host_free", "svg_cpulist_parse",
     # sublong's voting step (include/subread_long.h)
     "svg_long_vote_batch", "svg_long_free",
@@ -161,6 +163,19 @@ def lib():
             L.svg_cell_set_exons.restype = i32
             L.svg_cell_align_timing.argtypes = [vp, vp]
             L.svg_cell_align_timing.restype = i32
+        if hasattr(L, "svg_cell_assign_batch"):
+            L.svg_cell_set_annotation.argtypes = [vp, vp, u64, i32]
+            L.svg_cell_set_annotation.restype = i32
+            L.svg_cell_set_barcodes.argtypes = [vp, vp, u64, i32]
+            L.svg_cell_set_barcodes.restype = i32
+            L.svg_cell_assign_batch.argtypes = [vp] * 5
+            L.svg_cell_assign_batch.restype = i32
+            L.svg_cell_assign_free.argtypes = [vp]
+            L.svg_cell_assign_records.argtypes = [vp, vp, u64, vp]
+            L.svg_cell_assign_records.restype = i32
+            L.svg_cell_hits_free.argtypes = [vp]
+            L.svg_cell_assign_timing.argtypes = [vp, vp]
+            L.svg_cell_assign_timing.restype = i32
         if hasattr(L, "svg_long_vote_batch"):   # (older builds loaded side by side for A/B runs lack it)
             L.svg_long_vote_batch.argtypes = [vp] * 3
             L.svg_long_vote_batch.restype = i32
@@ -596,6 +611,69 @@ class VoteIndex:
             raise ValueError("set_cell_exons: starts and stops must be 1-d arrays of one length")
         _check(lib().svg_cell_set_exons(self.h, a.ctypes.data, b.ctypes.data, ctypes.c_uint64(len(a))),
                "svg_cell_set_exons")
+
+    def set_cell_annotation(self, features, allow_multi_overlap=False):
+        """svg_cell_set_annotation: the features in annotation-file order as a CELL_FEATURE_DTYPE
+        array (contig = index into the index's .reads table, start and end 1-based inclusive,
+        gene = the caller's gene number); builds the reference's sorted feature table, blocks and
+        reverse tables and fills the exon planes.  An empty array clears both."""
+        from .abi import CELL_FEATURE_DTYPE
+        f = np.ascontiguousarray(features, dtype=CELL_FEATURE_DTYPE)
+        if f.ndim != 1:
+            raise ValueError("set_cell_annotation: features must be a 1-d CELL_FEATURE_DTYPE array")
+        _check(lib().svg_cell_set_annotation(self.h, f.ctypes.data, ctypes.c_uint64(len(f)), int(bool(allow_multi_overlap))),
+               "svg_cell_set_annotation")
+
+    def set_cell_barcodes(self, barcodes):
+        """svg_cell_set_barcodes: the whitelist as a sequence of str / bytes of one length (2..16,
+        A/C/G/T, distinct); an empty sequence clears it."""
+        bs = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+        arr = (ctypes.c_char_p * max(1, len(bs)))(*bs)
+        _check(lib().svg_cell_set_barcodes(self.h, arr, ctypes.c_uint64(len(bs)), len(bs[0]) if bs else 0),
+               "svg_cell_set_barcodes")
+
+    def cell_assign(self, packed_reads, barcodes=None, **params):
+        """svg_cell_assign_batch: cell_align, then the gene assignment of every record and the cell
+        barcode of every read -> (heads, alns, hits, genes, cell_barcode_no).  barcodes: a PackedBatch
+        of the reads' cell barcodes (the whitelist's length each) or None.  hits: one CELL_HIT_DTYPE
+        per record, its genes at genes[first_gene : first_gene + nhits]."""
+        from .abi import SvgCellAlignParams, SvgCellAssigned
+        p = SvgCellAlignParams()
+        lib().svg_cell_align_params_default(ctypes.byref(p))
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("cell_assign: no parameter %r" % k)
+            setattr(p, k, int(v))
+        s = packed_reads.struct()
+        b = barcodes.struct() if barcodes is not None else None
+        res = SvgCellAssigned()
+        rc = lib().svg_cell_assign_batch(self.h, ctypes.byref(p), ctypes.byref(s), ctypes.byref(b) if b is not None else None,
+                                         ctypes.byref(res))
+        _check(rc, "svg_cell_assign_batch")
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_assign_free(ctypes.byref(res))
+
+    def cell_assign_records(self, alns):
+        """svg_cell_assign_records: the assignment over CELL_ALN_DTYPE records held by the caller
+        -> (hits, genes)."""
+        from .abi import CELL_ALN_DTYPE, SvgCellHits
+        a = np.ascontiguousarray(alns, dtype=CELL_ALN_DTYPE)
+        res = SvgCellHits()
+        _check(lib().svg_cell_assign_records(self.h, a.ctypes.data, ctypes.c_uint64(len(a)), ctypes.byref(res)),
+               "svg_cell_assign_records")
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_hits_free(ctypes.byref(res))
+
+    def cell_assign_timing(self):
+        """svg_cell_assign_timing: ms of the assign kernel, the barcode kernel and the gene scan +
+        compact, summed since the last call, under set_timing(True)."""
+        ms = (ctypes.c_double * 3)()
+        _check(lib().svg_cell_assign_timing(self.h, ms), "svg_cell_assign_timing")
+        return dict(zip(("assign", "barcode", "scan_compact"), (float(x) for x in ms)))
 
     def long_vote(self, reads):
         """svg_long_vote_batch: sublong's voting step (LRMdo_one_voting_read + the copy and location

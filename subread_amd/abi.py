@@ -225,6 +225,42 @@ class SvgCellAlns(ctypes.Structure):
         return h, a
 
 
+# svg_cell_feature / svg_cell_hit (include/subread_vote.h): what svg_cell_set_annotation takes per
+# feature and what svg_cell_assign_batch returns per alignment record
+CELL_FEATURE_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("gene", "<i4"),
+                               ("is_negative_strand", "u1"), ("_pad", "u1", (3,))])
+CELL_HIT_DTYPE = np.dtype([("contig", "<i4"), ("chro_pos", "<i4"), ("nhits", "<u4"), ("_pad", "<u4"),
+                           ("first_gene", "<u8")])
+CELL_MAX_GENES = 16
+assert CELL_FEATURE_DTYPE.itemsize == 20 and CELL_HIT_DTYPE.itemsize == 24
+
+
+class SvgCellHits(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_genes", ctypes.c_uint64),
+                ("hits", ctypes.c_void_p), ("genes", ctypes.c_void_p)]
+
+    def arrays(self):
+        """Copies of the hit records and the flat gene list."""
+        h = np.zeros(self.n_records, dtype=CELL_HIT_DTYPE)
+        g = np.zeros(self.n_genes, dtype=np.int32)
+        if self.n_records:
+            ctypes.memmove(h.ctypes.data, self.hits, h.nbytes)
+        if self.n_genes:
+            ctypes.memmove(g.ctypes.data, self.genes, g.nbytes)
+        return h, g
+
+
+class SvgCellAssigned(ctypes.Structure):
+    _fields_ = [("alns", SvgCellAlns), ("hits", SvgCellHits), ("cell_barcode_no", ctypes.c_void_p)]
+
+    def arrays(self):
+        """(heads, alns, hits, genes, cell_barcode_no) as numpy arrays."""
+        b = np.zeros(self.alns.n_reads, dtype=np.int32)
+        if self.alns.n_reads:
+            ctypes.memmove(b.ctypes.data, self.cell_barcode_no, b.nbytes)
+        return self.alns.arrays() + self.hits.arrays() + (b,)
+
+
 # svg_long_vote (include/subread_long.h): one used slot of sublong's LRMgene_vote_t
 LONG_VOTE_DTYPE = np.dtype([("pos", "<u4"), ("coverage_start", "<u4"), ("coverage_end", "<u4"),
                             ("votes", "<u2"), ("negative", "u1"), ("_pad", "u1"), ("slot", "<u4")])

@@ -37,4 +37,18 @@ __device__ __forceinline__ uint64_t cell_read_base(const CellParams &cp, uint32_
 // cell_probe_kernel and cell_tally_kernel for one chunk on st: heads (first_slot unset) and the
 // reads' 51 staging records each; mid (or NULL) is recorded between the two kernels
 void cell_launch_vote(const CellParams &cp, int img, int n_cu, hipStream_t st, hipEvent_t mid = NULL);
+
+// svg_cell_assign.hip behind svg_cell_align.hip's chunk loop (svg_cell_assign_batch): begin uploads
+// the read barcodes (bc may be NULL) and takes the chunk buffers; chunk assigns the `used` records
+// of the chunk that lie compacted at d_recs and the barcodes of its k reads from first_read on, and
+// appends them to the run's host arrays; end hands the arrays over (hits and barcode_no NULL: frees
+// them) and releases the run
+struct CellAssignRun;
+int  cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st,
+                       CellAssignRun **out);
+int  cell_assign_chunk(CellAssignRun *run, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used);
+void cell_assign_end(CellAssignRun *run, svg_cell_hits *hits, int32_t **barcode_no);
+// svg_cell_align_batch's body; run != NULL: with the assignment behind every chunk
+int  cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
+                    const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no);
 #endif

@@ -657,7 +657,7 @@ extern "C" int svg_cell_set_exons(svg_index *h, const uint32_t *starts, const ui
 	return 0;
 }
 
-static int align_params_check(const svg_cell_align_params *p)
+static int align_params_check(const svg_cell_align_params *p, const char *who)
 {
 	struct { const char *name; int v, lo, hi; } f[] = {
 		{"total_subreads", p->total_subreads, 7, C_SUB},                                              // :547
@@ -670,7 +670,7 @@ static int align_params_check(const svg_cell_align_params *p)
 	};
 	for (size_t i = 0; i < sizeof f / sizeof f[0]; i++)
 		if (f[i].v < f[i].lo || f[i].v > f[i].hi) {
-			svg_set_error("svg_cell_align_batch: %s %d outside %d..%d", f[i].name, f[i].v, f[i].lo, f[i].hi);
+			svg_set_error("%s: %s %d outside %d..%d", who, f[i].name, f[i].v, f[i].lo, f[i].hi);
 			return SVG_E_ARG;
 		}
 	return 0;
@@ -678,30 +678,37 @@ static int align_params_check(const svg_cell_align_params *p)
 
 extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res)
 {
-	if (!h || !p || !reads || !res) { svg_set_error("svg_cell_align_batch: NULL argument"); return SVG_E_ARG; }
+	return cell_align_run(h, p, reads, res, NULL, NULL, NULL);
+}
+
+int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
+                   const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no)
+{
+	const char *who = hits ? "svg_cell_assign_batch" : "svg_cell_align_batch";   // the entry point named in error texts
+	if (!h || !p || !reads || !res) { svg_set_error("%s: NULL argument", who); return SVG_E_ARG; }
 	memset(res, 0, sizeof *res);
 	if (h->nblocks > 1) {
-		svg_set_error("svg_cell_align_batch: an index of %d blocks (cellCounts takes a one-block index)", h->nblocks);
+		svg_set_error("%s: an index of %d blocks (cellCounts takes a one-block index)", who, h->nblocks);
 		return SVG_E_UNSUPPORTED;
 	}
-	int rc = align_params_check(p);
+	int rc = align_params_check(p, who);
 	if (rc) return rc;
 	if (h->dix.start_base_offset & 3u) {
-		svg_set_error("svg_cell_align_batch: an .array image that starts at base %u (not a multiple of 4)", h->dix.start_base_offset);
+		svg_set_error("%s: an .array image that starts at base %u (not a multiple of 4)", who, h->dix.start_base_offset);
 		return SVG_E_UNSUPPORTED;
 	}
 	const uint64_t n = reads->n_reads;
 	if (n == 0) return 0;
-	if (!reads->bases || !reads->lens) { svg_set_error("svg_cell_align_batch: NULL read buffer"); return SVG_E_ARG; }
+	if (!reads->bases || !reads->lens) { svg_set_error("%s: NULL read buffer", who); return SVG_E_ARG; }
 	uint64_t nbases = 0;
 	for (uint64_t r = 0; r < n; r++) {
 		if (reads->lens[r] > SVG_CELL_MAX_READ_LENGTH) {
-			svg_set_error("svg_cell_align_batch: read %llu has %d bases (at most %d)", (unsigned long long)r, (int)reads->lens[r],
+			svg_set_error("%s: read %llu has %d bases (at most %d)", who, (unsigned long long)r, (int)reads->lens[r],
 			              SVG_CELL_MAX_READ_LENGTH);
 			return SVG_E_ARG;
 		}
 		if (!reads->starts && reads->lens[r] > reads->stride) {
-			svg_set_error("svg_cell_align_batch: read %llu is longer than the stride", (unsigned long long)r);
+			svg_set_error("%s: read %llu is longer than the stride", who, (unsigned long long)r);
 			return SVG_E_ARG;
 		}
 		const uint64_t e = (reads->starts ? reads->starts[r] : r * reads->stride) + reads->lens[r];
@@ -738,16 +745,18 @@ extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p
 	            (xw && hipMemsetAsync((char *)d[D_XMASK] + xw, 0, 8, st) != hipSuccess) ||
 	            (reads->starts && hipMemcpyAsync(d[D_STARTS], reads->starts, 8 * n, hipMemcpyHostToDevice, st) != hipSuccess) ||
 	            hipMemcpyAsync(d[D_LENS], reads->lens, 2 * n, hipMemcpyHostToDevice, st) != hipSuccess)) {
-		svg_set_error("svg_cell_align_batch: upload failed");
+		svg_set_error("%s: upload failed", who);
 		rc = SVG_E_DEVICE;
 	}
-	if (!rc && hipMemsetAsync(d[D_TOTAL], 0, 16, st) != hipSuccess) { svg_set_error("svg_cell_align_batch: upload failed"); rc = SVG_E_DEVICE; }
+	if (!rc && hipMemsetAsync(d[D_TOTAL], 0, 16, st) != hipSuccess) { svg_set_error("%s: upload failed", who); rc = SVG_E_DEVICE; }
 	// svg_set_timing: events around each launch, summed per kernel (svg_cell_align_timing)
 	hipEvent_t ev[7] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL};
 	if (!rc && h->timing)
 		for (int i = 0; i < 7; i++)
-			if (hipEventCreate(&ev[i]) != hipSuccess) { svg_set_error("svg_cell_align_batch: hipEventCreate failed"); rc = SVG_E_DEVICE; break; }
+			if (hipEventCreate(&ev[i]) != hipSuccess) { svg_set_error("%s: hipEventCreate failed", who); rc = SVG_E_DEVICE; break; }
 	const int img = key_image(h);
+	CellAssignRun *run = NULL;
+	if (!rc && hits) rc = cell_assign_begin(h, bc, n, m, R, st, &run);
 	for (uint64_t o = 0; o < n && !rc; o += m) {
 		const uint64_t k = n - o < m ? n - o : m;
 		AlignParams ap;
@@ -802,13 +811,13 @@ extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p
 		if (hipGetLastError() != hipSuccess ||
 		    hipMemcpyAsync(res->heads + o, d[D_AHEADS], sizeof(svg_cell_aln_head) * k, hipMemcpyDeviceToHost, st) != hipSuccess ||
 		    hipMemcpyAsync(tot, d[D_TOTAL], 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-			svg_set_error("svg_cell_align_batch: HIP error %s", hipGetErrorString(hipGetLastError()));
+			svg_set_error("%s: HIP error %s", who, hipGetErrorString(hipGetLastError()));
 			rc = SVG_E_DEVICE;
 			break;
 		}
 		const uint64_t used = tot[0];
 		if (tot[1]) {
-			svg_set_error("svg_cell_align_batch: %llu CIGAR texts longer than SVG_CELL_CIGAR", (unsigned long long)(uint32_t)tot[1]);
+			svg_set_error("%s: %llu CIGAR texts longer than SVG_CELL_CIGAR", who, (unsigned long long)(uint32_t)tot[1]);
 			rc = SVG_E_DEVICE;
 			break;
 		}
@@ -824,12 +833,14 @@ extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p
 			res->alns = g;
 		}
 		if (used && hipMemcpy(res->alns + nrec, d[D_COMPACT], sizeof(svg_cell_aln) * used, hipMemcpyDeviceToHost) != hipSuccess) {
-			svg_set_error("svg_cell_align_batch: download failed");
+			svg_set_error("%s: download failed", who);
 			rc = SVG_E_DEVICE;
 			break;
 		}
+		if (run && (rc = cell_assign_chunk(run, o, k, (const svg_cell_aln *)d[D_COMPACT], used))) break;
 		nrec += used;
 	}
+	if (run) cell_assign_end(run, rc ? NULL : hits, rc ? NULL : barcode_no);
 	for (int i = 0; i < D_N; i++) hipFree(d[i]);
 	for (int i = 0; i < 7; i++)
 		if (ev[i]) hipEventDestroy(ev[i]);

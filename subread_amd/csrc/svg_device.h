@@ -195,6 +195,8 @@ struct svg_index {
 	uint32_t *d_exons;
 	// svg_cell_align_batch under svg_set_timing: ms per kernel (probe, tally, select, explain, emit, scan + compact)
 	double cell_ms[6];
+	// svg_cell_set_annotation's and svg_cell_set_barcodes' device images and the assign timing (svg_cell_assign.hip)
+	struct svg_cellassign *cas;
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { svg_set_error("HIP error %s at %s:%d", hipGetErrorString(_e), __FILE__, __LINE__); return SVG_E_DEVICE; } } while (0)
@@ -225,6 +227,8 @@ static inline int svg_ensure(svg_index *h, void **p, size_t *cap, size_t need)
 void svg_io_free(svg_index *h);
 // svg_long.hip
 void svg_long_ws_free(svg_index *h);
+// svg_cell_assign.hip
+void svg_cell_assign_ws_free(svg_index *h);
 
 // ---------------------------------------------------------------------------------------------
 // kernel parameters (passed by value)
