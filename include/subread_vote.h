@@ -554,6 +554,111 @@ void svg_cell_hits_free(svg_cell_hits *hits);
 int  svg_cell_assign_timing(svg_index *idx, double ms[3]);
 
 /*
+ * cellCounts' UMI stage: what cellCounts_do_one_batch (cell-counts.c:3951-4126) computes between
+ * reading a batch file and rewriting it, as a counter object in device memory beside a handle.
+ *
+ * An observation is one (sample, cell, gene, UMI): the reference makes one per (written record,
+ * gene of its list) with ADD_key_struct (:3945-3949, :4011-4026).  svg_cell_counter_finish runs
+ *   1. the support count: the number of observations of every distinct (sample, cell, gene, UMI)
+ *      (the string table of :3991 and cellCounts_do_one_batch_tab_to_struct_list, :3756-3775);
+ *   2. step 1 (:4057-4058): per sample the entries by (cell, gene, support descending, UMI by
+ *      memcmp) (the comparator of :3725-3754, a total order on distinct entries), then within each
+ *      (cell, gene) section, in that order, an entry is merged into the first accepted entry at
+ *      Hamming distance < 2 (cellCounts_hamming_max2_fixlen, :3511), whose support grows by the
+ *      entry's; otherwise it is accepted (cellCounts_do_one_batch_UMI_merge_one_cell, :3552-3641).
+ *      In a section of at most 30 entries "first" is the acceptance order (:3598-3620).  In a
+ *      larger one (sec_end - sec_start > 30, :3555) it is the acceptance order among the acceptors
+ *      whose first L/2 characters equal the entry's, and only if none of those is near, among the
+ *      acceptors whose characters L/2 .. 2*(L/2)-1 equal the entry's (:3566-3597); for odd L the
+ *      last character is in neither key.  The two rules pick different acceptors;
+ *   3. step 2 (:4062-4064): the survivors by (cell, UMI, support descending, gene); a (cell, UMI)
+ *      section of one entry counts 1 for its (cell, gene) (:3672); in a larger one the first counts
+ *      1 only if its support is strictly greater than the second's, else removed_umis grows by one
+ *      (:3532-3538); every other entry of the section is dropped;
+ *   4. the (cell, gene) -> number of UMIs table (ADD_count_hash, :3520, written at :4068-4069).
+ * Read as written and kept: the keys put into filtered_CGU_table are formatted after cellbc was
+ * set to -1 (:3581-3587, :3540-3546), so the lookup of :4095-4102 never finds them for a real cell
+ * and the replacement UMI is dead in the reference; this interface reports the acceptor's UMI per
+ * entry and rewrites no read bin.
+ *
+ * Key fields (an observation is two 64-bit words): sample 1..255 (8 bits, at most n_samples), cell
+ * 0..2^24-1 (24 bits: a whitelist of 2^23 barcodes fits), gene 0..2^31-1 (32 bits), the UMI as 3
+ * bits a base with A < C < G < N < T (42 bits for SVG_CELL_MAX_UMI bases, so that an unsigned
+ * compare of codes is memcmp of the text); a support is a uint32_t, and a counter holds fewer than
+ * 2^31 observations (SVG_E_UNSUPPORTED beyond).  svg_cell_counter_add refuses a value outside its
+ * field, and a UMI character other than A/C/G/T/N, with SVG_E_ARG and appends nothing;
+ * svg_cell_count_batch counts such values on the device and svg_cell_counter_finish then fails
+ * with SVG_E_ARG, on every call until svg_cell_counter_reset (the counter cannot tell which of its
+ * observations the refused ones would have been).  Both paths check the fields before they drop
+ * anything: sample 0 with a cell of 2^24 is refused, not dropped.  Never truncated.  An observation whose sample is <= 0, or whose cell is < 0
+ * (both merge steps skip cell -1, :3658), is dropped and tallied (dropped_no_sample first,
+ * dropped_no_cell second).
+ *
+ * svg_cell_count_batch runs svg_cell_assign_batch's chunk loop and, while a chunk's hits, gene lists
+ * and barcode numbers are in device memory, appends one observation per (record, gene) of every
+ * read: a record with contig -1 or nhits 0 gives none.  umis: `umi_length` bases per read, the
+ * exception bit meaning N; sample_no: one int32 per read, cellCounts_get_sample_id's 1-based
+ * answer, <= 0 for none.  res == NULL: nothing per read comes back; else res is exactly what
+ * svg_cell_assign_batch returns.  The store grows by reallocation (SVG_E_NOMEM when the device
+ * refuses, or past option cell_count_max_mb); a failed call leaves the counter as it was before.
+ *
+ * svg_cell_counter_finish answers for everything added since create or reset, may be called again,
+ * and add / count_batch after it go on accumulating.  counts: ascending (sample, cell, gene), sample
+ * s (1-based) at counts[count_first[s-1] .. count_first[s]) (the reference writes hash-iteration
+ * order).  want_entries: one svg_cell_umi_entry per distinct (sample, cell, gene, UMI) in step 1's
+ * order, sample s at entries[entry_first[s-1] .. entry_first[s]).
+ * svg_cell_count_timing (under svg_set_timing) returns and resets the summed milliseconds of:
+ * expand, sort + run-length (support count and step 1's order), step 1 lane kernel, step 1 wave
+ * kernel, step 2 (sort + flags), count table.
+ */
+#define SVG_CELL_MAX_UMI        14   /* MAX_UMI_LEN */
+#define SVG_CELL_MAX_SAMPLES    255
+#define SVG_CELL_MAX_CELLS      (1 << 24)
+#define SVG_CELL_UMI_COUNTED    0    /* counts 1 for its (cell, gene) */
+#define SVG_CELL_UMI_MERGED     1    /* merged into acceptor_umi in step 1 */
+#define SVG_CELL_UMI_LOST       2    /* not the first of its (cell, UMI) section in step 2 */
+#define SVG_CELL_UMI_REMOVED    3    /* the first of its section, its support not above the second's */
+
+typedef struct svg_cell_counter svg_cell_counter;
+
+typedef struct svg_cell_count {
+	int32_t  sample, cell, gene;
+	uint32_t n_umis;
+} svg_cell_count;                     /* 16 bytes */
+
+typedef struct svg_cell_umi_entry {
+	int32_t  sample, cell, gene;
+	uint32_t support;                 /* before step 1 */
+	uint32_t support_merged;          /* after step 1 (an acceptor's has grown) */
+	uint32_t outcome;                 /* SVG_CELL_UMI_* */
+	char     umi[SVG_CELL_MAX_UMI];            /* zero to the end */
+	char     acceptor_umi[SVG_CELL_MAX_UMI];   /* SVG_CELL_UMI_MERGED only, else zero */
+} svg_cell_umi_entry;                 /* 52 bytes */
+
+typedef struct svg_cell_counts {
+	uint32_t n_samples, umi_length;
+	uint64_t n_counts, n_entries;
+	svg_cell_count *counts;
+	uint64_t *count_first;            /* [n_samples + 1] */
+	uint64_t *removed_umis;           /* [n_samples] */
+	svg_cell_umi_entry *entries;      /* NULL without want_entries */
+	uint64_t *entry_first;            /* [n_samples + 1] */
+	uint64_t dropped_no_sample, dropped_no_cell;
+} svg_cell_counts;
+
+int  svg_cell_counter_create(svg_index *idx, int umi_length, int n_samples, svg_cell_counter **out);
+void svg_cell_counter_free(svg_cell_counter *c);
+int  svg_cell_counter_reset(svg_cell_counter *c);
+int  svg_cell_counter_add(svg_cell_counter *c, const int32_t *sample, const int32_t *cell, const int64_t *gene,
+                          const char *umi_text, uint64_t n);
+int  svg_cell_count_batch(svg_index *idx, const svg_cell_align_params *p, const svg_packed_reads *reads,
+                          const svg_packed_reads *barcodes, const svg_packed_reads *umis, const int32_t *sample_no,
+                          svg_cell_counter *c, svg_cell_assigned *res);
+int  svg_cell_counter_finish(svg_cell_counter *c, int want_entries, svg_cell_counts *out);
+void svg_cell_counts_free(svg_cell_counts *out);
+int  svg_cell_count_timing(svg_index *idx, double ms[6]);
+
+/*
  * Fragile junction voting of subjunc reads longer than 160 bases (core_fragile_junction_voting,
  * core-junction.c:5151-5422; do_voting runs it for every index block, strand and read end,
  * core.c:3138-3142).  The read (strand 0: as fetched after the -S reversal, strand 1: its
@@ -685,6 +790,8 @@ int  svg_cpulist_parse(const char *list, uint8_t *mask, int max);
  *                               out statically before its work counter (default 6 single-end,
  *                               0 pairs)
  *   keys_literal, long_probes   svg_probe_keys / svg_long_vote_batch variants
+ *   cell_count_max_mb           the most device memory a svg_cell_counter's observations may take
+ *                               (SVG_E_NOMEM beyond; 0: what the device gives)
  *   debug, pipe_debug, long_debug  diagnostics on stderr
  * svg_set_option returns SVG_E_ARG for an unknown name; svg_get_option returns the current value
  * (0 for an unknown name). */

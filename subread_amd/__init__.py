@@ -38,6 +38,8 @@ EXPORTS = [
     "svg_cell_align_timing",
     "svg_cell_set_annotation", "svg_cell_set_barcodes", "svg_cell_assign_batch", "svg_cell_assign_free",
     "svg_cell_assign_records", "svg_cell_hits_free", "svg_cell_assign_timing",
+    "svg_cell_counter_create", "svg_cell_counter_free", "svg_cell_counter_reset", "svg_cell_counter_add",
+    "svg_cell_count_batch", "svg_cell_counter_finish", "svg_cell_counts_free", "svg_cell_count_timing",
     "svg_host_placement", "svg_host_alloc", "svg_host_free", "svg_cpulist_parse",
     # sublong's voting step (include/subread_long.h)
     "svg_long_vote_batch", "svg_long_free",
@@ -176,6 +178,23 @@ def lib():
             L.svg_cell_hits_free.argtypes = [vp]
             L.svg_cell_assign_timing.argtypes = [vp, vp]
             L.svg_cell_assign_timing.restype = i32
+        if hasattr(L, "svg_cell_count_batch"):
+            L.svg_cell_counter_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
+            L.svg_cell_counter_create.restype = i32
+            L.svg_cell_counter_free.argtypes = [vp]
+            L.svg_cell_counter_free.restype = None
+            L.svg_cell_counter_reset.argtypes = [vp]
+            L.svg_cell_counter_reset.restype = i32
+            L.svg_cell_counter_add.argtypes = [vp, vp, vp, vp, vp, u64]
+            L.svg_cell_counter_add.restype = i32
+            L.svg_cell_count_batch.argtypes = [vp] * 8
+            L.svg_cell_count_batch.restype = i32
+            L.svg_cell_counter_finish.argtypes = [vp, i32, vp]
+            L.svg_cell_counter_finish.restype = i32
+            L.svg_cell_counts_free.argtypes = [vp]
+            L.svg_cell_counts_free.restype = None
+            L.svg_cell_count_timing.argtypes = [vp, vp]
+            L.svg_cell_count_timing.restype = i32
         if hasattr(L, "svg_long_vote_batch"):   # (older builds loaded side by side for A/B runs lack it)
             L.svg_long_vote_batch.argtypes = [vp] * 3
             L.svg_long_vote_batch.restype = i32
@@ -229,7 +248,9 @@ def lib():
 def _check(rc, what):
     if rc != 0:
         msg = lib().svg_last_error().decode(errors="replace")
-        raise SvgError("%s failed: %s (%s)" % (what, ERRORS.get(rc, rc), msg))
+        e = SvgError("%s failed: %s (%s)" % (what, ERRORS.get(rc, rc), msg))
+        e.rc = rc          # the SVG_E_* code
+        raise e
 
 
 def set_option(name, value):
@@ -439,6 +460,93 @@ class _HostMem:
             pass
 
 
+class CellCounter:
+    """svg_cell_counter (include/subread_vote.h): the observations (sample, cell, gene, UMI) of
+    cellCounts_do_one_batch in device memory, and its support count, two merge steps and count
+    table on the device."""
+
+    def __init__(self, index, umi_length, n_samples=1):
+        self.index, self.umi_length, self.n_samples = index, int(umi_length), int(n_samples)
+        c = ctypes.c_void_p()
+        _check(lib().svg_cell_counter_create(index.h, self.umi_length, self.n_samples, ctypes.byref(c)), "svg_cell_counter_create")
+        self.c = c
+        index._counters.add(self)     # VoteIndex.close frees the counters it still has
+
+    def close(self):
+        if self.c:
+            lib().svg_cell_counter_free(self.c)
+            self.c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(lib().svg_cell_counter_reset(self.c), "svg_cell_counter_reset")
+
+    def add(self, sample, cell, gene, umis):
+        """svg_cell_counter_add: observations held on the host; umis is an (n, umi_length) uint8
+        array, an 'S<umi_length>' array or a sequence of str / bytes."""
+        s = np.ascontiguousarray(sample, dtype=np.int32)
+        c = np.ascontiguousarray(cell, dtype=np.int32)
+        g = np.ascontiguousarray(gene, dtype=np.int64)
+        if isinstance(umis, np.ndarray) and umis.dtype == np.uint8:
+            u = np.ascontiguousarray(umis)
+        else:
+            u = np.frombuffer(b"".join(x.encode() if isinstance(x, str) else bytes(x) for x in umis), np.uint8)
+        if not (len(s) == len(c) == len(g)) or u.size != len(s) * self.umi_length:
+            raise ValueError("CellCounter.add: arrays of different lengths")
+        _check(lib().svg_cell_counter_add(self.c, s.ctypes.data, c.ctypes.data, g.ctypes.data, u.ctypes.data,
+                                          ctypes.c_uint64(len(s))), "svg_cell_counter_add")
+
+    def count_batch(self, packed_reads, barcodes, umis, sample_no, want_result=False, **params):
+        """svg_cell_count_batch: cell_assign's chunk loop with the observations of every chunk
+        appended on the device.  umis: a PackedBatch of umi_length bases per read; sample_no: one
+        int32 per read (1-based, <= 0: none).  want_result: also return what cell_assign returns;
+        otherwise nothing per read comes back and the answer is None."""
+        from .abi import SvgCellAlignParams, SvgCellAssigned
+        p = SvgCellAlignParams()
+        lib().svg_cell_align_params_default(ctypes.byref(p))
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("count_batch: no parameter %r" % k)
+            setattr(p, k, int(v))
+        s = packed_reads.struct()
+        b = barcodes.struct() if barcodes is not None else None
+        u = umis.struct()
+        sn = np.ascontiguousarray(sample_no, dtype=np.int32)
+        if len(sn) != len(packed_reads):
+            raise ValueError("count_batch: one sample number per read")
+        res = SvgCellAssigned() if want_result else None
+        rc = lib().svg_cell_count_batch(self.index.h, ctypes.byref(p), ctypes.byref(s), ctypes.byref(b) if b is not None else None,
+                                        ctypes.byref(u), sn.ctypes.data, self.c, ctypes.byref(res) if want_result else None)
+        _check(rc, "svg_cell_count_batch")
+        if not want_result:
+            return None
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_assign_free(ctypes.byref(res))
+
+    def finish(self, want_entries=False):
+        """svg_cell_counter_finish -> the dict of SvgCellCounts.arrays()."""
+        from .abi import SvgCellCounts
+        out = SvgCellCounts()
+        _check(lib().svg_cell_counter_finish(self.c, int(bool(want_entries)), ctypes.byref(out)), "svg_cell_counter_finish")
+        try:
+            return out.arrays()
+        finally:
+            lib().svg_cell_counts_free(ctypes.byref(out))
+
+    def timing(self):
+        """svg_cell_count_timing: ms per stage summed since the last call, under set_timing(True)."""
+        ms = (ctypes.c_double * 6)()
+        _check(lib().svg_cell_count_timing(self.index.h, ms), "svg_cell_count_timing")
+        return dict(zip(("expand", "sort_rle", "step1_lane", "step1_wave", "step2", "count_table"), (float(x) for x in ms)))
+
+
 class VoteIndex:
     """An index resident in HBM of one GPU (svg_index_open / svg_index_build*)."""
 
@@ -524,8 +632,17 @@ class VoteIndex:
 
     def close(self):
         if getattr(self, "h", None):
+            for c in list(getattr(self, "_counter_set", ())):     # a counter holds its handle: free it first
+                c.close()
             lib().svg_index_close(self.h)
             self.h = None
+
+    @property
+    def _counters(self):
+        if getattr(self, "_counter_set", None) is None:
+            import weakref
+            self._counter_set = weakref.WeakSet()
+        return self._counter_set
 
     def __del__(self):
         try:
@@ -674,6 +791,10 @@ class VoteIndex:
         ms = (ctypes.c_double * 3)()
         _check(lib().svg_cell_assign_timing(self.h, ms), "svg_cell_assign_timing")
         return dict(zip(("assign", "barcode", "scan_compact"), (float(x) for x in ms)))
+
+    def cell_counter(self, umi_length, n_samples=1):
+        """svg_cell_counter_create: cellCounts' UMI stage beside this handle -> a CellCounter."""
+        return CellCounter(self, umi_length, n_samples)
 
     def long_vote(self, reads):
         """svg_long_vote_batch: sublong's voting step (LRMdo_one_voting_read + the copy and location

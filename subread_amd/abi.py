@@ -261,6 +261,40 @@ class SvgCellAssigned(ctypes.Structure):
         return self.alns.arrays() + self.hits.arrays() + (b,)
 
 
+# svg_cell_count / svg_cell_umi_entry (include/subread_vote.h): what svg_cell_counter_finish returns:
+# the (cell, gene) -> UMIs table and, on request, one record per distinct (sample, cell, gene, UMI)
+CELL_MAX_UMI, CELL_MAX_SAMPLES, CELL_MAX_CELLS = 14, 255, 1 << 24
+CELL_UMI_COUNTED, CELL_UMI_MERGED, CELL_UMI_LOST, CELL_UMI_REMOVED = 0, 1, 2, 3
+CELL_COUNT_DTYPE = np.dtype([("sample", "<i4"), ("cell", "<i4"), ("gene", "<i4"), ("n_umis", "<u4")])
+CELL_UMI_ENTRY_DTYPE = np.dtype([("sample", "<i4"), ("cell", "<i4"), ("gene", "<i4"), ("support", "<u4"),
+                                 ("support_merged", "<u4"), ("outcome", "<u4"), ("umi", "S%d" % CELL_MAX_UMI),
+                                 ("acceptor_umi", "S%d" % CELL_MAX_UMI)])
+assert CELL_COUNT_DTYPE.itemsize == 16 and CELL_UMI_ENTRY_DTYPE.itemsize == 52
+
+
+class SvgCellCounts(ctypes.Structure):
+    _fields_ = [("n_samples", ctypes.c_uint32), ("umi_length", ctypes.c_uint32), ("n_counts", ctypes.c_uint64),
+                ("n_entries", ctypes.c_uint64), ("counts", ctypes.c_void_p), ("count_first", ctypes.c_void_p),
+                ("removed_umis", ctypes.c_void_p), ("entries", ctypes.c_void_p), ("entry_first", ctypes.c_void_p),
+                ("dropped_no_sample", ctypes.c_uint64), ("dropped_no_cell", ctypes.c_uint64)]
+
+    def arrays(self):
+        """A dict of copies: counts, count_first, removed_umis, entries (None without want_entries),
+        entry_first, dropped_no_sample, dropped_no_cell."""
+        def copy(ptr, n, dt):
+            a = np.zeros(n, dtype=dt)
+            if n and ptr:
+                ctypes.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+        s = int(self.n_samples)
+        return {"counts": copy(self.counts, self.n_counts, CELL_COUNT_DTYPE),
+                "count_first": copy(self.count_first, s + 1, np.uint64),
+                "removed_umis": copy(self.removed_umis, s, np.uint64),
+                "entries": copy(self.entries, self.n_entries, CELL_UMI_ENTRY_DTYPE) if self.entries else None,
+                "entry_first": copy(self.entry_first, s + 1, np.uint64),
+                "dropped_no_sample": int(self.dropped_no_sample), "dropped_no_cell": int(self.dropped_no_cell)}
+
+
 # svg_long_vote (include/subread_long.h): one used slot of sublong's LRMgene_vote_t
 LONG_VOTE_DTYPE = np.dtype([("pos", "<u4"), ("coverage_start", "<u4"), ("coverage_end", "<u4"),
                             ("votes", "<u2"), ("negative", "u1"), ("_pad", "u1"), ("slot", "<u4")])

@@ -45,10 +45,24 @@ void cell_launch_vote(const CellParams &cp, int img, int n_cu, hipStream_t st, h
 // them) and releases the run
 struct CellAssignRun;
 int  cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st,
-                       CellAssignRun **out);
+                       CellAssignRun **out, bool quiet = false);
 int  cell_assign_chunk(CellAssignRun *run, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used);
 void cell_assign_end(CellAssignRun *run, svg_cell_hits *hits, int32_t **barcode_no);
-// svg_cell_align_batch's body; run != NULL: with the assignment behind every chunk
+// the chunk's buffers in device memory after cell_assign_chunk: hits of its records, its compacted
+// gene lists (n_genes numbers, the first being number gene_base of the run) and its reads' barcode
+// numbers (NULL: no whitelist or no barcodes)
+void cell_assign_view(CellAssignRun *run, const svg_cell_hit **d_hits, const int32_t **d_genes, uint64_t *gene_base, uint64_t *n_genes,
+                      const int32_t **d_bc);
+// svg_cell_count.hip behind the assignment (svg_cell_count_batch): begin uploads the reads' UMIs and
+// sample numbers; chunk appends the chunk's observations to the counter
+struct CellCountSink;
+int  cell_count_begin(CellCountSink *sink, uint64_t n, hipStream_t st);
+int  cell_count_chunk(CellCountSink *sink, uint64_t first_read, uint64_t k, const svg_cell_aln_head *d_heads, uint64_t rec_base,
+                      const svg_cell_hit *d_hits, const int32_t *d_genes, uint64_t gene_base, uint64_t n_genes, const int32_t *d_bc,
+                      hipStream_t st);
+// svg_cell_align_batch's body; hits != NULL: with the assignment behind every chunk; sink != NULL:
+// with the counter behind that; quiet: nothing per read is downloaded and res, hits and barcode_no
+// stay empty
 int  cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
-                    const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no);
+                    const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no, CellCountSink *sink = NULL, bool quiet = false);
 #endif

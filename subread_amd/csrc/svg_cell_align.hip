@@ -682,9 +682,9 @@ extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p
 }
 
 int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
-                   const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no)
+                   const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no, CellCountSink *sink, bool quiet)
 {
-	const char *who = hits ? "svg_cell_assign_batch" : "svg_cell_align_batch";   // the entry point named in error texts
+	const char *who = sink ? "svg_cell_count_batch" : hits ? "svg_cell_assign_batch" : "svg_cell_align_batch";   // the entry point named in error texts
 	if (!h || !p || !reads || !res) { svg_set_error("%s: NULL argument", who); return SVG_E_ARG; }
 	memset(res, 0, sizeof *res);
 	if (h->nblocks > 1) {
@@ -737,8 +737,8 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 		if (!sizes[i]) continue;
 		if (!(rc = dmalloc(h, &d[i], sizes[i]))) held += sizes[i];
 	}
-	res->heads = (svg_cell_aln_head *)malloc(sizeof(svg_cell_aln_head) * n);
-	if (!rc && !res->heads) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; }
+	if (!quiet) res->heads = (svg_cell_aln_head *)malloc(sizeof(svg_cell_aln_head) * n);
+	if (!rc && !quiet && !res->heads) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; }
 	if (!rc && (hipMemcpyAsync(d[D_BASES], reads->bases, bw, hipMemcpyHostToDevice, st) != hipSuccess ||
 	            hipMemsetAsync((char *)d[D_BASES] + bw, 0, 8, st) != hipSuccess ||
 	            (xw && hipMemcpyAsync(d[D_XMASK], reads->xmask, xw, hipMemcpyHostToDevice, st) != hipSuccess) ||
@@ -756,7 +756,8 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 			if (hipEventCreate(&ev[i]) != hipSuccess) { svg_set_error("%s: hipEventCreate failed", who); rc = SVG_E_DEVICE; break; }
 	const int img = key_image(h);
 	CellAssignRun *run = NULL;
-	if (!rc && hits) rc = cell_assign_begin(h, bc, n, m, R, st, &run);
+	if (!rc && hits) rc = cell_assign_begin(h, bc, n, m, R, st, &run, quiet);
+	if (!rc && sink) rc = cell_count_begin(sink, n, st);
 	for (uint64_t o = 0; o < n && !rc; o += m) {
 		const uint64_t k = n - o < m ? n - o : m;
 		AlignParams ap;
@@ -809,7 +810,7 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 		if (ev[6]) hipEventRecord(ev[6], st);
 		uint64_t tot[2] = {0, 0};
 		if (hipGetLastError() != hipSuccess ||
-		    hipMemcpyAsync(res->heads + o, d[D_AHEADS], sizeof(svg_cell_aln_head) * k, hipMemcpyDeviceToHost, st) != hipSuccess ||
+		    (!quiet && hipMemcpyAsync(res->heads + o, d[D_AHEADS], sizeof(svg_cell_aln_head) * k, hipMemcpyDeviceToHost, st) != hipSuccess) ||
 		    hipMemcpyAsync(tot, d[D_TOTAL], 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
 			svg_set_error("%s: HIP error %s", who, hipGetErrorString(hipGetLastError()));
 			rc = SVG_E_DEVICE;
@@ -826,26 +827,34 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 				float ms = 0;
 				if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) h->cell_ms[i] += ms;
 			}
-		if (nrec + used > cap) {
+		if (!quiet && nrec + used > cap) {
 			cap = nrec + used + used * ((n - o - k + k - 1) / k);
 			svg_cell_aln *g = (svg_cell_aln *)realloc(res->alns, sizeof(svg_cell_aln) * cap);
 			if (!g) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; break; }
 			res->alns = g;
 		}
-		if (used && hipMemcpy(res->alns + nrec, d[D_COMPACT], sizeof(svg_cell_aln) * used, hipMemcpyDeviceToHost) != hipSuccess) {
+		if (!quiet && used && hipMemcpy(res->alns + nrec, d[D_COMPACT], sizeof(svg_cell_aln) * used, hipMemcpyDeviceToHost) != hipSuccess) {
 			svg_set_error("%s: download failed", who);
 			rc = SVG_E_DEVICE;
 			break;
 		}
 		if (run && (rc = cell_assign_chunk(run, o, k, (const svg_cell_aln *)d[D_COMPACT], used))) break;
+		if (sink) {
+			const svg_cell_hit *d_hits;
+			const int32_t *d_genes, *d_bc;
+			uint64_t gene_base, n_genes;
+			cell_assign_view(run, &d_hits, &d_genes, &gene_base, &n_genes, &d_bc);
+			if ((rc = cell_count_chunk(sink, o, k, (const svg_cell_aln_head *)d[D_AHEADS], nrec, d_hits, d_genes, gene_base, n_genes, d_bc, st))) break;
+		}
 		nrec += used;
 	}
-	if (run) cell_assign_end(run, rc ? NULL : hits, rc ? NULL : barcode_no);
+	if (run) cell_assign_end(run, rc || quiet ? NULL : hits, rc || quiet ? NULL : barcode_no);
 	for (int i = 0; i < D_N; i++) hipFree(d[i]);
 	for (int i = 0; i < 7; i++)
 		if (ev[i]) hipEventDestroy(ev[i]);
 	h->device_bytes -= held;
 	if (rc) { svg_cell_align_free(res); return rc; }
+	if (quiet) return 0;
 	res->n_reads = n;
 	res->n_records = nrec;
 	return 0;

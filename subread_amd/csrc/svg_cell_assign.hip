@@ -374,6 +374,8 @@ struct CellAssignRun {
 	int32_t *genes, *bc;
 	uint64_t n_hits, cap_hits, n_genes, cap_genes;
 	hipEvent_t ev[5];
+	bool quiet;               // svg_cell_count_batch without a result: the host arrays stay empty
+	uint64_t chunk_gene_base, chunk_genes;   // of the last chunk (cell_assign_view)
 };
 
 static void run_free(CellAssignRun *r)
@@ -408,18 +410,18 @@ static int run_buffers(CellAssignRun *r, uint64_t cap_recs)
 	return 0;
 }
 
-int cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st, CellAssignRun **out)
+int cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st, CellAssignRun **out, bool quiet)
 {
 	*out = NULL;
 	svg_cellassign *ca = cas_get(h);
 	if (!ca) return SVG_E_NOMEM;
 	CellAssignRun *r = (CellAssignRun *)calloc(1, sizeof *r);
 	if (!r) { svg_set_error("out of host memory"); return SVG_E_NOMEM; }
-	r->h = h; r->st = st; r->n = n;
+	r->h = h; r->st = st; r->n = n; r->quiet = quiet;
 	r->have_bc = bc && ca->bt.n;
 	int rc = run_buffers(r, chunk * (uint64_t)max_report);
-	r->bc = (int32_t *)malloc(4 * (n ? n : 1));
-	if (!rc && !r->bc) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; }
+	if (!quiet) r->bc = (int32_t *)malloc(4 * (n ? n : 1));
+	if (!rc && !quiet && !r->bc) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; }
 	if (!rc && r->have_bc) {
 		const uint32_t L = ca->bt.length;
 		uint64_t nbases = 0;
@@ -483,14 +485,14 @@ static int run_records(CellAssignRun *r, const svg_cell_aln *d_recs, uint64_t us
 	hipLaunchKernelGGL(assign_compact_kernel, dim3((unsigned)((used * A_GENES + 255) / 256)), dim3(256), 0, st, ap);
 	if (r->ev[0]) hipEventRecord(r->ev[3], st);
 	uint64_t tot[2] = {0, 0};
-	if (r->n_hits + used > r->cap_hits) {
+	if (!r->quiet && r->n_hits + used > r->cap_hits) {
 		const uint64_t cap = (r->n_hits + used) * 2;
 		svg_cell_hit *g = (svg_cell_hit *)realloc(r->hits, sizeof(svg_cell_hit) * cap);
 		if (!g) { svg_set_error("out of host memory"); return SVG_E_NOMEM; }
 		r->hits = g; r->cap_hits = cap;
 	}
 	if (hipGetLastError() != hipSuccess ||
-	    hipMemcpyAsync(r->hits + r->n_hits, r->d_hits, sizeof(svg_cell_hit) * used, hipMemcpyDeviceToHost, st) != hipSuccess ||
+	    (!r->quiet && hipMemcpyAsync(r->hits + r->n_hits, r->d_hits, sizeof(svg_cell_hit) * used, hipMemcpyDeviceToHost, st) != hipSuccess) ||
 	    hipMemcpyAsync(tot, r->d_total, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
 		svg_set_error("svg_cell_assign: HIP error %s", hipGetErrorString(hipGetLastError()));
 		return SVG_E_DEVICE;
@@ -506,6 +508,9 @@ static int run_records(CellAssignRun *r, const svg_cell_aln *d_recs, uint64_t us
 		if (hipEventElapsedTime(&ms, r->ev[2], r->ev[3]) == hipSuccess) ca->ms[2] += ms;
 	}
 	const uint64_t ng = tot[0];
+	r->chunk_gene_base = r->n_genes;
+	r->chunk_genes = ng;
+	if (r->quiet) { r->n_hits += used; r->n_genes += ng; return 0; }
 	if (r->n_genes + ng > r->cap_genes) {
 		const uint64_t cap = (r->n_genes + ng) * 2;
 		int32_t *g = (int32_t *)realloc(r->genes, 4 * cap);
@@ -540,12 +545,14 @@ int cell_assign_chunk(CellAssignRun *r, uint64_t first_read, uint64_t k, const s
 		hipLaunchKernelGGL(barcode_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, r->st, bp);
 		if (r->ev[0]) hipEventRecord(r->ev[1], r->st);
 		if (hipGetLastError() != hipSuccess ||
-		    hipMemcpyAsync(r->bc + first_read, r->d_bc, 4 * k, hipMemcpyDeviceToHost, r->st) != hipSuccess) {
+		    (!r->quiet && hipMemcpyAsync(r->bc + first_read, r->d_bc, 4 * k, hipMemcpyDeviceToHost, r->st) != hipSuccess)) {
 			svg_set_error("svg_cell_assign_batch: HIP error %s", hipGetErrorString(hipGetLastError()));
 			return SVG_E_DEVICE;
 		}
-	} else
+	} else if (!r->quiet)
 		for (uint64_t i = 0; i < k; i++) r->bc[first_read + i] = -1;
+	r->chunk_gene_base = r->n_genes;
+	r->chunk_genes = 0;
 	int rc = run_records(r, d_recs, used, r->have_bc);
 	if (rc) return rc;
 	if (!used && r->have_bc) {
@@ -554,6 +561,16 @@ int cell_assign_chunk(CellAssignRun *r, uint64_t first_read, uint64_t k, const s
 		if (r->ev[0] && hipEventElapsedTime(&ms, r->ev[0], r->ev[1]) == hipSuccess) ca->ms[1] += ms;
 	}
 	return 0;
+}
+
+void cell_assign_view(CellAssignRun *r, const svg_cell_hit **d_hits, const int32_t **d_genes, uint64_t *gene_base, uint64_t *n_genes,
+                      const int32_t **d_bc)
+{
+	*d_hits = (const svg_cell_hit *)r->d_hits;
+	*d_genes = (const int32_t *)r->d_genes;
+	*gene_base = r->chunk_gene_base;
+	*n_genes = r->chunk_genes;
+	*d_bc = r->have_bc ? (const int32_t *)r->d_bc : NULL;
 }
 
 void cell_assign_end(CellAssignRun *r, svg_cell_hits *hits, int32_t **barcode_no)

@@ -197,6 +197,9 @@ struct svg_index {
 	double cell_ms[6];
 	// svg_cell_set_annotation's and svg_cell_set_barcodes' device images and the assign timing (svg_cell_assign.hip)
 	struct svg_cellassign *cas;
+	// svg_cell_count_batch and svg_cell_counter_finish under svg_set_timing (svg_cell_count.hip): expand, sort + run-length,
+	// step 1 lane kernel, step 1 wave kernel, step 2, count table
+	double cellcount_ms[6];
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { svg_set_error("HIP error %s at %s:%d", hipGetErrorString(_e), __FILE__, __LINE__); return SVG_E_DEVICE; } } while (0)
