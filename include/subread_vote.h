@@ -659,6 +659,113 @@ void svg_cell_counts_free(svg_cell_counts *out);
 int  svg_cell_count_timing(svg_index *idx, double ms[6]);
 
 /*
+ * Read names to barcode, UMI and sample number.  In cellCounts every read carries its cell barcode,
+ * UMI and sample index in its name: the readers compose it (cell-counts.c:2191-2242 from BCL,
+ * "R%011llu:<barcode+UMI>|<their qualities>|<index>|<its qualities>|@RgLater@L%03d"; input-blc.c:
+ * 1779-1829 from FASTQ, "R%011lld|<barcode+UMI>|<qualities>|<index>|<qualities>" or
+ * "...|input#%04d@L%03d") and cellCounts_vote_and_add_count takes it apart for every written record
+ * (:1955-1976) with cellCounts_scan_read_name_str (:1658-1696) and cellCounts_get_sample_id
+ * (:1862-1880).  Here the names go in as text (a svg_reads: NUL-free names, offsets, lengths) and the
+ * device does that work, one lane per name.
+ *
+ * The scan, as written: from the name's second character on, '|' separates, and in
+ * SVG_CELL_NAMES_BCL mode ':' does too (:1663) -- also a ':' inside the quality text, which a
+ * quality '9' becomes under the increment of :2229; this is kept.  Separator 1: the trimmed name
+ * length is its position, the barcode starts behind it and the UMI barcode_length further on;
+ * separator 3: the sample text behind it; separator 5: the lane text behind it, past a leading
+ * "@RgLater@" (:1679), and the scan stops.  `fields` is the scan's return value.
+ * Lane number: the digits from the lane text's second character to the first non-digit (:1967-1971).
+ * Sample with a lane text (:1972, cellCounts_get_sample_id): the sheet rows in order, a row whose lane
+ * is SVG_CELL_LANE_ALL or the read's; a dual row (index longer than 12, :664) by
+ * hamming_dist_ATGC_max1_2p <= 2, a single one by hamming_dist_ATGC_max1 <= 1 (input-blc.c:
+ * 1072-1105).  Both compare up to the first character is_ATGC rejects in either string (it accepts N;
+ * in the read's text that is the '|' behind the index, or the name's end), so over the shorter of the
+ * two; _2p splits that length in halves and allows one mismatch in each; max1 gives up at two.  The
+ * first matching row wins, no row gives -1.
+ * Sample without a lane text (:1973-1975): a sample text starting "input#" takes the four characters
+ * behind it as decimal digits, plus 1, as a 1-based sheet line: lines[line - 1], 0 where the line is
+ * absent or beyond n_lines.  Any other sample text gives -1 (:1976).  lane is -1 without a lane text.
+ *
+ * svg_cell_set_samples: rows is sample_barcode_list in its order (sheet_convert_ss_to_arr,
+ * :648-668: the caller parses the sheet), index texts of A/C/G/T, 1..SVG_CELL_MAX_INDEX characters
+ * (both indexes of a dual row back to back, as :659-663 store them); at most SVG_CELL_MAX_ROWS rows
+ * and lines.  A later call replaces everything; n_rows = n_lines = 0 clears it.  SVG_E_ARG: a sample
+ * number outside 1..n_samples in a row (0..n_samples in lines), n_samples outside
+ * 1..SVG_CELL_MAX_SAMPLES, another character, an empty or over-long index, too many rows.
+ *
+ * Outside the reference's contract, defined here: status SVG_CELL_NAME_FEW_FIELDS, fewer than 3
+ * separators (the reference then reads through a NULL sample text); SVG_CELL_NAME_PAST_END, the
+ * barcode or the UMI runs past the name's end; SVG_CELL_NAME_BAD_CHAR, a barcode or UMI character
+ * other than A/C/G/T/N.  Such a name is refused: sample_no -1, lane -1, barcode and UMI all A.
+ * Characters beyond a name's end read as NUL.  umi_length < 1 (the reference's auto-detection,
+ * :1684-1693) is SVG_E_ARG, as are barcode_length outside 1..16 and umi_length above
+ * SVG_CELL_MAX_UMI.  A lane number of more than nine digits is outside the contract (int overflow in
+ * the reference); here it wraps as unsigned arithmetic.
+ *
+ * svg_cell_parse_names returns every field per read: barcodes and umis are svg_packed_reads of
+ * stride SVG_CELL_NAME_STRIDE (starts NULL, the exception bit meaning N), the layout
+ * svg_cell_count_batch takes; `refused` counts the names with a status.  Free with svg_cell_names_free.
+ *
+ * svg_cell_count_names_batch is svg_cell_count_batch with the names in the place of barcodes, UMIs
+ * and sample numbers: the same chunk loop (one body), the parse kernel in front of every chunk, its
+ * output read by the barcode kernel, the expand kernel and the tallies while it is in device memory;
+ * nothing of it comes to the host.  The barcode length is the whitelist's (no whitelist: SVG_E_ARG,
+ * the UMI's place in the name would be unknown), the UMI length is the counter's, and the sheet's
+ * n_samples is at most the counter's.  A refused name gives no
+ * observation and no tally; it is counted on the device and svg_cell_counter_finish fails with
+ * SVG_E_ARG until svg_cell_counter_reset, as for a value outside its key field.
+ *
+ * svg_cell_counter_tallies: reads_per_sample, mapped_reads_per_sample and assigned_reads_per_sample
+ * (:1993-2004; the SampleTable of :4433-4453), n_samples + 1 numbers each, accumulated on the device
+ * by svg_cell_count_batch and svg_cell_count_names_batch (not by svg_cell_counter_add, which sees no
+ * records) and cleared by reset.  They count calls of cellCounts_vote_and_add_count, not reads:
+ * cellCounts_select_and_write_alignments (:2700-2716) calls the writer once per record with
+ * this_multi_mapping_i = reporting_this_alignment_no + 1, and since the records with a score > 0
+ * sort first and reporting_multi_alignment_no counts them, the records of a read are numbered
+ * 1, 2, ... without a gap; a read without a record gets one call with reporting_index -1.  A record
+ * whose position locate_gene_position does not place (contig -1) is turned into that same unmapped
+ * call at :2067/:2087 (reporting_index -1, nhits 0, this_multi_mapping_i 0), record by record.  So
+ * with sample_no > 0: reads[sample_no - 1] grows by the read's records (1 without any); mapped by 1
+ * if the read's first record has a contig; assigned by 1 if that record's nhits (after :1982) is
+ * above 0.  A second record never counts as mapped, so a read whose first record has contig -1 is
+ * not mapped whatever follows.  With sample_no <= 0 the calls go to reads[n_samples]; mapped and
+ * assigned have nothing there.  A sample number above n_samples is tallied nowhere.
+ * svg_cell_names_timing (under svg_set_timing) returns and resets the parse kernel's milliseconds.
+ */
+#define SVG_CELL_NAMES_BCL        0    /* GENE_INPUT_BCL: ':' separates too */
+#define SVG_CELL_NAMES_FASTQ      1    /* GENE_INPUT_SCRNA_FASTQ */
+#define SVG_CELL_LANE_ALL         99999   /* LANE_FOR_ALL_LANES */
+#define SVG_CELL_MAX_INDEX        32
+#define SVG_CELL_MAX_ROWS         65536
+#define SVG_CELL_NAME_STRIDE      32
+#define SVG_CELL_NAME_OK          0
+#define SVG_CELL_NAME_FEW_FIELDS  1
+#define SVG_CELL_NAME_PAST_END    2
+#define SVG_CELL_NAME_BAD_CHAR    3
+
+typedef struct svg_cell_sample_row {
+	int32_t lane;                     /* or SVG_CELL_LANE_ALL */
+	int32_t sample_no;                /* 1-based */
+	const char *index;                /* NUL-terminated */
+} svg_cell_sample_row;
+
+typedef struct svg_cell_names {
+	uint64_t n_reads, refused;
+	int32_t *fields, *trimmed_len, *lane, *sample_no;
+	uint32_t *status;                 /* SVG_CELL_NAME_* */
+	svg_packed_reads barcodes, umis;  /* stride SVG_CELL_NAME_STRIDE */
+} svg_cell_names;
+
+int  svg_cell_set_samples(svg_index *idx, const svg_cell_sample_row *rows, uint64_t n_rows, const int32_t *lines, uint64_t n_lines,
+                          int n_samples);
+int  svg_cell_parse_names(svg_index *idx, const svg_reads *names, int mode, int barcode_length, int umi_length, svg_cell_names *out);
+void svg_cell_names_free(svg_cell_names *out);
+int  svg_cell_count_names_batch(svg_index *idx, const svg_cell_align_params *p, const svg_packed_reads *reads, const svg_reads *names,
+                                int mode, svg_cell_counter *c, svg_cell_assigned *res);
+int  svg_cell_counter_tallies(svg_cell_counter *c, uint64_t *reads, uint64_t *mapped, uint64_t *assigned);
+int  svg_cell_names_timing(svg_index *idx, double *ms);
+
+/*
  * Fragile junction voting of subjunc reads longer than 160 bases (core_fragile_junction_voting,
  * core-junction.c:5151-5422; do_voting runs it for every index block, strand and read end,
  * core.c:3138-3142).  The read (strand 0: as fetched after the -S reversal, strand 1: its

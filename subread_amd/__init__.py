@@ -40,6 +40,8 @@ EXPORTS = [
     "svg_cell_assign_records", "svg_cell_hits_free", "svg_cell_assign_timing",
     "svg_cell_counter_create", "svg_cell_counter_free", "svg_cell_counter_reset", "svg_cell_counter_add",
     "svg_cell_count_batch", "svg_cell_counter_finish", "svg_cell_counts_free", "svg_cell_count_timing",
+    "svg_cell_set_samples", "svg_cell_parse_names", "svg_cell_names_free", "svg_cell_count_names_batch", "svg_cell_counter_tallies",
+    "svg_cell_names_timing",
     "svg_host_placement", "svg_host_alloc", "svg_host_free", "svg_cpulist_parse",
     # sublong's voting step (include/subread_long.h)
     "svg_long_vote_batch", "svg_long_free",
@@ -195,6 +197,19 @@ def lib():
             L.svg_cell_counts_free.restype = None
             L.svg_cell_count_timing.argtypes = [vp, vp]
             L.svg_cell_count_timing.restype = i32
+        if hasattr(L, "svg_cell_parse_names"):
+            L.svg_cell_set_samples.argtypes = [vp, vp, u64, vp, u64, i32]
+            L.svg_cell_set_samples.restype = i32
+            L.svg_cell_parse_names.argtypes = [vp, vp, i32, i32, i32, vp]
+            L.svg_cell_parse_names.restype = i32
+            L.svg_cell_names_free.argtypes = [vp]
+            L.svg_cell_names_free.restype = None
+            L.svg_cell_count_names_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+            L.svg_cell_count_names_batch.restype = i32
+            L.svg_cell_counter_tallies.argtypes = [vp, vp, vp, vp]
+            L.svg_cell_counter_tallies.restype = i32
+            L.svg_cell_names_timing.argtypes = [vp, vp]
+            L.svg_cell_names_timing.restype = i32
         if hasattr(L, "svg_long_vote_batch"):   # (older builds loaded side by side for A/B runs lack it)
             L.svg_long_vote_batch.argtypes = [vp] * 3
             L.svg_long_vote_batch.restype = i32
@@ -530,6 +545,36 @@ class CellCounter:
         finally:
             lib().svg_cell_assign_free(ctypes.byref(res))
 
+    def count_names_batch(self, packed_reads, names, mode, want_result=False, **params):
+        """svg_cell_count_names_batch: count_batch with the read names (a ReadBatch of text) in the
+        place of barcodes, UMIs and sample numbers; the parse kernel runs in front of every chunk.
+        mode: abi.CELL_NAMES_BCL or abi.CELL_NAMES_FASTQ."""
+        from .abi import SvgCellAlignParams, SvgCellAssigned
+        p = SvgCellAlignParams()
+        lib().svg_cell_align_params_default(ctypes.byref(p))
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("count_names_batch: no parameter %r" % k)
+            setattr(p, k, int(v))
+        s, nm = packed_reads.struct(), names.struct()
+        res = SvgCellAssigned() if want_result else None
+        rc = lib().svg_cell_count_names_batch(self.index.h, ctypes.byref(p), ctypes.byref(s), ctypes.byref(nm), int(mode), self.c,
+                                              ctypes.byref(res) if want_result else None)
+        _check(rc, "svg_cell_count_names_batch")
+        if not want_result:
+            return None
+        try:
+            return res.arrays()
+        finally:
+            lib().svg_cell_assign_free(ctypes.byref(res))
+
+    def tallies(self):
+        """svg_cell_counter_tallies -> dict of reads, mapped, assigned: n_samples + 1 uint64 each
+        (the last slot: calls of reads without a sample)."""
+        t = np.zeros((3, self.n_samples + 1), np.uint64)
+        _check(lib().svg_cell_counter_tallies(self.c, t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data), "svg_cell_counter_tallies")
+        return {"reads": t[0], "mapped": t[1], "assigned": t[2]}
+
     def finish(self, want_entries=False):
         """svg_cell_counter_finish -> the dict of SvgCellCounts.arrays()."""
         from .abi import SvgCellCounts
@@ -791,6 +836,39 @@ class VoteIndex:
         ms = (ctypes.c_double * 3)()
         _check(lib().svg_cell_assign_timing(self.h, ms), "svg_cell_assign_timing")
         return dict(zip(("assign", "barcode", "scan_compact"), (float(x) for x in ms)))
+
+    def set_cell_samples(self, rows, lines=(), n_samples=1):
+        """svg_cell_set_samples: rows is a sequence of (lane, sample_no, index text) in the order of
+        the reference's sample_barcode_list (lane abi.CELL_LANE_ALL: every lane); lines[i] is the
+        sample number of sheet line i + 1 (0: absent).  No rows and no lines clears the sheet."""
+        from .abi import SvgCellSampleRow
+        rows = list(rows)
+        arr = (SvgCellSampleRow * max(1, len(rows)))()
+        keep = []
+        for i, (lane, sample, text) in enumerate(rows):
+            keep.append(text.encode() if isinstance(text, str) else bytes(text))
+            arr[i].lane, arr[i].sample_no, arr[i].index = int(lane), int(sample), keep[-1]
+        ln = np.ascontiguousarray(lines, dtype=np.int32)
+        _check(lib().svg_cell_set_samples(self.h, arr if rows else None, len(rows), ln.ctypes.data if len(ln) else None, len(ln), int(n_samples)),
+               "svg_cell_set_samples")
+
+    def cell_parse_names(self, names, mode, barcode_length, umi_length):
+        """svg_cell_parse_names over a ReadBatch of name text -> the dict of SvgCellNames.arrays()."""
+        from .abi import SvgCellNames
+        out = SvgCellNames()
+        s = names.struct()
+        _check(lib().svg_cell_parse_names(self.h, ctypes.byref(s), int(mode), int(barcode_length), int(umi_length), ctypes.byref(out)),
+               "svg_cell_parse_names")
+        try:
+            return out.arrays()
+        finally:
+            lib().svg_cell_names_free(ctypes.byref(out))
+
+    def cell_names_timing(self):
+        """svg_cell_names_timing: the parse kernel's ms summed since the last call, under set_timing(True)."""
+        ms = ctypes.c_double()
+        _check(lib().svg_cell_names_timing(self.h, ctypes.byref(ms)), "svg_cell_names_timing")
+        return float(ms.value)
 
     def cell_counter(self, umi_length, n_samples=1):
         """svg_cell_counter_create: cellCounts' UMI stage beside this handle -> a CellCounter."""

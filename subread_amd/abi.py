@@ -295,6 +295,38 @@ class SvgCellCounts(ctypes.Structure):
                 "dropped_no_sample": int(self.dropped_no_sample), "dropped_no_cell": int(self.dropped_no_cell)}
 
 
+# svg_cell_set_samples / svg_cell_parse_names (include/subread_vote.h)
+CELL_NAMES_BCL, CELL_NAMES_FASTQ, CELL_LANE_ALL, CELL_MAX_INDEX, CELL_NAME_STRIDE = 0, 1, 99999, 32, 32
+CELL_NAME_OK, CELL_NAME_FEW_FIELDS, CELL_NAME_PAST_END, CELL_NAME_BAD_CHAR = 0, 1, 2, 3
+
+
+class SvgCellSampleRow(ctypes.Structure):
+    _fields_ = [("lane", ctypes.c_int32), ("sample_no", ctypes.c_int32), ("index", ctypes.c_char_p)]
+
+
+class SvgCellNames(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint64), ("refused", ctypes.c_uint64), ("fields", ctypes.c_void_p), ("trimmed_len", ctypes.c_void_p),
+                ("lane", ctypes.c_void_p), ("sample_no", ctypes.c_void_p), ("status", ctypes.c_void_p), ("barcodes", SvgPackedReads),
+                ("umis", SvgPackedReads)]
+
+    def arrays(self):
+        """A dict of copies: fields, trimmed_len, lane, sample_no (int32), status (uint32), refused, and
+        barcodes and umis as PackedBatch of stride CELL_NAME_STRIDE (the exception bit: N)."""
+        n = int(self.n_reads)
+
+        def copy(ptr, count, dt):
+            a = np.zeros(count, dtype=dt)
+            if count and ptr:
+                ctypes.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+
+        def packed(s):
+            return PackedBatch(copy(s.bases, 2 * n, np.uint32), copy(s.xmask, n, np.uint32), None, CELL_NAME_STRIDE, copy(s.lens, n, np.uint16))
+        return {"fields": copy(self.fields, n, np.int32), "trimmed_len": copy(self.trimmed_len, n, np.int32), "lane": copy(self.lane, n, np.int32),
+                "sample_no": copy(self.sample_no, n, np.int32), "status": copy(self.status, n, np.uint32), "refused": int(self.refused),
+                "barcodes": packed(self.barcodes), "umis": packed(self.umis)}
+
+
 # svg_long_vote (include/subread_long.h): one used slot of sublong's LRMgene_vote_t
 LONG_VOTE_DTYPE = np.dtype([("pos", "<u4"), ("coverage_start", "<u4"), ("coverage_end", "<u4"),
                             ("votes", "<u2"), ("negative", "u1"), ("_pad", "u1"), ("slot", "<u4")])

@@ -44,9 +44,14 @@ void cell_launch_vote(const CellParams &cp, int img, int n_cu, hipStream_t st, h
 // appends them to the run's host arrays; end hands the arrays over (hits and barcode_no NULL: frees
 // them) and releases the run
 struct CellAssignRun;
+// device_bc: the barcodes are not uploaded; every chunk's lie in device memory (d_bases and d_xmask of
+// cell_assign_chunk: read i of the chunk at base i * SVG_CELL_NAME_STRIDE)
 int  cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st,
-                       CellAssignRun **out, bool quiet = false);
-int  cell_assign_chunk(CellAssignRun *run, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used);
+                       CellAssignRun **out, bool quiet = false, bool device_bc = false);
+int  cell_assign_chunk(CellAssignRun *run, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used,
+                       const uint32_t *d_bases = NULL, const uint32_t *d_xmask = NULL);
+// the whitelist's barcode length; 0: no whitelist
+int  cell_assign_barcode_length(svg_index *h);
 void cell_assign_end(CellAssignRun *run, svg_cell_hits *hits, int32_t **barcode_no);
 // the chunk's buffers in device memory after cell_assign_chunk: hits of its records, its compacted
 // gene lists (n_genes numbers, the first being number gene_base of the run) and its reads' barcode
@@ -55,8 +60,13 @@ void cell_assign_view(CellAssignRun *run, const svg_cell_hit **d_hits, const int
                       const int32_t **d_bc);
 // svg_cell_count.hip behind the assignment (svg_cell_count_batch): begin uploads the reads' UMIs and
 // sample numbers; chunk appends the chunk's observations to the counter
+// (svg_cell_count_names_batch: begin uploads the names instead, and parse runs the parse kernel over
+// a chunk's names in front of cell_assign_chunk, whose barcodes are then the kernel's output)
 struct CellCountSink;
-int  cell_count_begin(CellCountSink *sink, uint64_t n, hipStream_t st);
+const char *cell_count_who(CellCountSink *sink);
+bool cell_count_has_names(CellCountSink *sink);
+int  cell_count_begin(CellCountSink *sink, uint64_t n, uint64_t chunk, hipStream_t st);
+int  cell_count_parse(CellCountSink *sink, uint64_t first_read, uint64_t k, const uint32_t **d_bc_bases, const uint32_t **d_bc_xmask);
 int  cell_count_chunk(CellCountSink *sink, uint64_t first_read, uint64_t k, const svg_cell_aln_head *d_heads, uint64_t rec_base,
                       const svg_cell_hit *d_hits, const int32_t *d_genes, uint64_t gene_base, uint64_t n_genes, const int32_t *d_bc,
                       hipStream_t st);
@@ -65,4 +75,22 @@ int  cell_count_chunk(CellCountSink *sink, uint64_t first_read, uint64_t k, cons
 // stay empty
 int  cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
                     const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no, CellCountSink *sink = NULL, bool quiet = false);
+// svg_cell_names.hip: the names of a batch in device memory and one chunk's parse output.  begin
+// uploads the text; chunk launches the parse kernel over k names (asynchronous on st); view gives the
+// chunk's output arrays (k entries each; the packed words at SVG_CELL_NAME_STRIDE bases a name) and
+// the run's count of refused names; time adds the last chunk's kernel time once st is idle
+struct CellNamesRun;
+struct CellNamesView {
+	const int32_t *fields, *trimmed, *lane, *sample;
+	const uint32_t *status, *bc_bases, *bc_xmask, *umi_bases, *umi_xmask;
+	unsigned long long *refused;
+};
+int  cell_names_begin(svg_index *h, const char *who, const svg_reads *names, int mode, int bl, int ul, uint64_t n, uint64_t chunk, hipStream_t st,
+                      CellNamesRun **out);
+int  cell_names_chunk(CellNamesRun *run, uint64_t first_read, uint64_t k);
+void cell_names_view(CellNamesRun *run, CellNamesView *v);
+void cell_names_time(CellNamesRun *run);
+void cell_names_end(CellNamesRun *run);
+// svg_cell_set_samples' n_samples; 0: no sheet
+int  cell_names_samples(svg_index *h);
 #endif

@@ -684,7 +684,7 @@ extern "C" int svg_cell_align_batch(svg_index *h, const svg_cell_align_params *p
 int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, svg_cell_alns *res,
                    const svg_packed_reads *bc, svg_cell_hits *hits, int32_t **barcode_no, CellCountSink *sink, bool quiet)
 {
-	const char *who = sink ? "svg_cell_count_batch" : hits ? "svg_cell_assign_batch" : "svg_cell_align_batch";   // the entry point named in error texts
+	const char *who = sink ? cell_count_who(sink) : hits ? "svg_cell_assign_batch" : "svg_cell_align_batch";   // the entry point named in error texts
 	if (!h || !p || !reads || !res) { svg_set_error("%s: NULL argument", who); return SVG_E_ARG; }
 	memset(res, 0, sizeof *res);
 	if (h->nblocks > 1) {
@@ -756,8 +756,8 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 			if (hipEventCreate(&ev[i]) != hipSuccess) { svg_set_error("%s: hipEventCreate failed", who); rc = SVG_E_DEVICE; break; }
 	const int img = key_image(h);
 	CellAssignRun *run = NULL;
-	if (!rc && hits) rc = cell_assign_begin(h, bc, n, m, R, st, &run, quiet);
-	if (!rc && sink) rc = cell_count_begin(sink, n, st);
+	if (!rc && hits) rc = cell_assign_begin(h, bc, n, m, R, st, &run, quiet, sink && cell_count_has_names(sink));
+	if (!rc && sink) rc = cell_count_begin(sink, n, m, st);
 	for (uint64_t o = 0; o < n && !rc; o += m) {
 		const uint64_t k = n - o < m ? n - o : m;
 		AlignParams ap;
@@ -838,7 +838,9 @@ int cell_align_run(svg_index *h, const svg_cell_align_params *p, const svg_packe
 			rc = SVG_E_DEVICE;
 			break;
 		}
-		if (run && (rc = cell_assign_chunk(run, o, k, (const svg_cell_aln *)d[D_COMPACT], used))) break;
+		const uint32_t *d_bcb = NULL, *d_bcx = NULL;
+		if (sink && (rc = cell_count_parse(sink, o, k, &d_bcb, &d_bcx))) break;
+		if (run && (rc = cell_assign_chunk(run, o, k, (const svg_cell_aln *)d[D_COMPACT], used, d_bcb, d_bcx))) break;
 		if (sink) {
 			const svg_cell_hit *d_hits;
 			const int32_t *d_genes, *d_bc;

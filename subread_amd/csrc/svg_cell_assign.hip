@@ -375,6 +375,7 @@ struct CellAssignRun {
 	uint64_t n_hits, cap_hits, n_genes, cap_genes;
 	hipEvent_t ev[5];
 	bool quiet;               // svg_cell_count_batch without a result: the host arrays stay empty
+	bool device_bc;           // the chunks' barcodes come from device memory (cell_assign_chunk)
 	uint64_t chunk_gene_base, chunk_genes;   // of the last chunk (cell_assign_view)
 };
 
@@ -410,7 +411,10 @@ static int run_buffers(CellAssignRun *r, uint64_t cap_recs)
 	return 0;
 }
 
-int cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st, CellAssignRun **out, bool quiet)
+int cell_assign_barcode_length(svg_index *h) { return h->cas && h->cas->bt.n ? (int)h->cas->bt.length : 0; }
+
+int cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint64_t chunk, int max_report, hipStream_t st, CellAssignRun **out, bool quiet,
+                      bool device_bc)
 {
 	*out = NULL;
 	svg_cellassign *ca = cas_get(h);
@@ -418,11 +422,13 @@ int cell_assign_begin(svg_index *h, const svg_packed_reads *bc, uint64_t n, uint
 	CellAssignRun *r = (CellAssignRun *)calloc(1, sizeof *r);
 	if (!r) { svg_set_error("out of host memory"); return SVG_E_NOMEM; }
 	r->h = h; r->st = st; r->n = n; r->quiet = quiet;
-	r->have_bc = bc && ca->bt.n;
+	r->have_bc = (bc || device_bc) && ca->bt.n;
+	r->device_bc = device_bc;
 	int rc = run_buffers(r, chunk * (uint64_t)max_report);
 	if (!quiet) r->bc = (int32_t *)malloc(4 * (n ? n : 1));
 	if (!rc && !quiet && !r->bc) { svg_set_error("out of host memory"); rc = SVG_E_NOMEM; }
-	if (!rc && r->have_bc) {
+	if (!rc && r->have_bc && device_bc) rc = run_alloc(r, &r->d_bc, 4 * chunk);
+	if (!rc && r->have_bc && !device_bc) {
 		const uint32_t L = ca->bt.length;
 		uint64_t nbases = 0;
 		if (!bc->bases || !bc->lens) { svg_set_error("svg_cell_assign_batch: NULL barcode buffer"); rc = SVG_E_ARG; }
@@ -526,7 +532,8 @@ static int run_records(CellAssignRun *r, const svg_cell_aln *d_recs, uint64_t us
 	return 0;
 }
 
-int cell_assign_chunk(CellAssignRun *r, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used)
+int cell_assign_chunk(CellAssignRun *r, uint64_t first_read, uint64_t k, const svg_cell_aln *d_recs, uint64_t used, const uint32_t *d_bases,
+                      const uint32_t *d_xmask)
 {
 	svg_cellassign *ca = r->h->cas;
 	if (used > r->cap_recs) { svg_set_error("svg_cell_assign: a chunk of %llu records", (unsigned long long)used); return SVG_E_DEVICE; }
@@ -539,6 +546,7 @@ int cell_assign_chunk(CellAssignRun *r, uint64_t first_read, uint64_t k, const s
 		bp.starts = r->d_starts ? (const uint64_t *)r->d_starts + first_read : NULL;
 		bp.stride = r->stride;
 		bp.base0 = first_read * r->stride;
+		if (r->device_bc) { bp.bases = d_bases; bp.xmask = d_xmask; bp.starts = NULL; bp.stride = SVG_CELL_NAME_STRIDE; bp.base0 = 0; }
 		bp.n = (uint32_t)k;
 		bp.out = (int32_t *)r->d_bc;
 		if (r->ev[0]) hipEventRecord(r->ev[0], r->st);

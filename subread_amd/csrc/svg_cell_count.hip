@@ -20,9 +20,14 @@ struct svg_cell_counter {
 	int L, n_samples;
 	uint64_t *d_hi, *d_lo;           // the observations: sample << 56 | cell << 32 | gene; the UMI code
 	uint64_t cap;
-	uint64_t cnt[4];                 // observations, dropped_no_sample, dropped_no_cell, values outside their fields
+	// observations, dropped_no_sample, dropped_no_cell, values outside their fields, refused read names; then
+	// the tallies reads, mapped and assigned, n_samples + 1 each (:1993-2004)
+	uint64_t *cnt;
 	unsigned long long *d_cnt;       // the same on the device
+	size_t cnt_bytes;
 };
+
+#define CNT_HEAD 5
 
 struct ExpandParams {
 	const svg_cell_aln_head *heads;  // the chunk's reads
@@ -30,6 +35,7 @@ struct ExpandParams {
 	const int32_t *genes;            // the chunk's gene lists
 	const int32_t *bc;               // the chunk's barcode numbers, or NULL
 	const int32_t *sample;           // the chunk's sample numbers
+	const uint32_t *status;          // the chunk's name statuses (svg_cell_count_names_batch), or NULL
 	const uint32_t *ubases, *uxmask;
 	const uint64_t *ustarts;
 	uint64_t ustride, ubase0, rec_base, gene_base, cap;
@@ -46,6 +52,7 @@ __global__ void __launch_bounds__(256) count_expand_kernel(ExpandParams ep)
 	if (r >= ep.n) return;
 	const svg_cell_aln_head hd = ep.heads[r];
 	if (!hd.n_records) return;
+	if (ep.status && ep.status[r]) return;        // a refused name: counted by count_tally_kernel
 	const uint64_t j0 = hd.first_record - ep.rec_base;
 	uint32_t total = 0;
 	for (uint32_t j = 0; j < hd.n_records; j++) {
@@ -84,6 +91,52 @@ __global__ void __launch_bounds__(256) count_expand_kernel(ExpandParams ep)
 			ep.lo[at] = code;
 			at++;
 		}
+	}
+}
+
+// lane = read: the tallies of :1993-2004 over the calls of cellCounts_vote_and_add_count that the read's
+// records stand for (subread_vote.h), and the refused names.  The lanes of a wave that share a
+// sample slot are summed first: one atomic per wave, slot and tally
+__global__ void __launch_bounds__(256) count_tally_kernel(ExpandParams ep)
+{
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	const bool live = r < ep.n;
+	const int S = ep.n_samples;
+	int slot = -1;
+	uint32_t calls = 0;
+	bool mapped = false, assigned = false, refused = false;
+	if (live) {
+		const svg_cell_aln_head hd = ep.heads[r];
+		const int32_t sample = ep.sample[r];
+		refused = ep.status && ep.status[r];
+		if (!refused && sample <= S) {
+			slot = sample > 0 ? sample - 1 : S;
+			calls = hd.n_records ? hd.n_records : 1u;
+			if (hd.n_records && sample > 0) {
+				const svg_cell_hit *h = ep.hits + (hd.first_record - ep.rec_base);
+				mapped = h->contig >= 0;
+				assigned = mapped && h->nhits > 0;
+			}
+		}
+	}
+	const uint32_t lane = threadIdx.x & 63u;
+	const unsigned long long nref = __ballot(refused);
+	if (nref && lane == 0) atomicAdd(ep.cnt + 4, (unsigned long long)__popcll(nref));
+	unsigned long long todo = __ballot(slot >= 0);
+	while (todo) {
+		const int s = __shfl(slot, __ffsll((long long)todo) - 1);
+		const bool mine = slot == s;
+		const unsigned long long same = __ballot(mine);
+		uint32_t sum = mine ? calls : 0u;
+		for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
+		const uint32_t nm = (uint32_t)__popcll(__ballot(mine && mapped)), na = (uint32_t)__popcll(__ballot(mine && assigned));
+		if (lane == 0) {
+			unsigned long long *t = ep.cnt + CNT_HEAD;
+			atomicAdd(t + s, (unsigned long long)sum);
+			if (nm) atomicAdd(t + (S + 1) + s, (unsigned long long)nm);
+			if (na) atomicAdd(t + 2 * (S + 1) + s, (unsigned long long)na);
+		}
+		todo &= ~same;
 	}
 }
 
@@ -338,10 +391,13 @@ extern "C" int svg_cell_counter_create(svg_index *h, int umi_length, int n_sampl
 	svg_cell_counter *c = (svg_cell_counter *)calloc(1, sizeof *c);
 	if (!c) { svg_set_error("out of host memory"); return SVG_E_NOMEM; }
 	c->h = h; c->L = umi_length; c->n_samples = n_samples;
+	c->cnt_bytes = 8 * (CNT_HEAD + 3 * ((size_t)n_samples + 1));
+	c->cnt = (uint64_t *)calloc(1, c->cnt_bytes);
+	if (!c->cnt) { free(c); svg_set_error("out of host memory"); return SVG_E_NOMEM; }
 	void *d = NULL;
-	int rc = hipSetDevice(h->device) == hipSuccess ? dmalloc(h, &d, 32) : SVG_E_DEVICE;
-	if (!rc && hipMemset(d, 0, 32) != hipSuccess) { svg_set_error("svg_cell_counter_create: HIP error"); rc = SVG_E_DEVICE; }
-	if (rc) { hipFree(d); free(c); return rc; }
+	int rc = hipSetDevice(h->device) == hipSuccess ? dmalloc(h, &d, c->cnt_bytes) : SVG_E_DEVICE;
+	if (!rc && hipMemset(d, 0, c->cnt_bytes) != hipSuccess) { svg_set_error("svg_cell_counter_create: HIP error"); rc = SVG_E_DEVICE; }
+	if (rc) { hipFree(d); free(c->cnt); free(c); return rc; }
 	c->d_cnt = (unsigned long long *)d;
 	*out = c;
 	return 0;
@@ -352,7 +408,8 @@ extern "C" void svg_cell_counter_free(svg_cell_counter *c)
 	if (!c) return;
 	hipSetDevice(c->h->device);
 	hipFree(c->d_hi); hipFree(c->d_lo); hipFree(c->d_cnt);
-	c->h->device_bytes -= 16 * c->cap + 32;
+	c->h->device_bytes -= 16 * c->cap + c->cnt_bytes;
+	free(c->cnt);
 	free(c);
 }
 
@@ -361,8 +418,8 @@ extern "C" int svg_cell_counter_reset(svg_cell_counter *c)
 	if (!c) { svg_set_error("svg_cell_counter_reset: NULL argument"); return SVG_E_ARG; }
 	int rc = counter_quiesce(c);
 	if (rc) return rc;
-	memset(c->cnt, 0, sizeof c->cnt);
-	HIPCHK(hipMemset(c->d_cnt, 0, 32));
+	memset(c->cnt, 0, c->cnt_bytes);
+	HIPCHK(hipMemset(c->d_cnt, 0, c->cnt_bytes));
 	return 0;
 }
 
@@ -405,16 +462,34 @@ extern "C" int svg_cell_counter_add(svg_cell_counter *c, const int32_t *sample, 
 	free(hi);
 	if (rc) return rc;
 	c->cnt[0] += m; c->cnt[1] += ds; c->cnt[2] += dc;
-	HIPCHK(hipMemcpy(c->d_cnt, c->cnt, 32, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(c->d_cnt, c->cnt, c->cnt_bytes, hipMemcpyHostToDevice));
+	return 0;
+}
+
+extern "C" int svg_cell_counter_tallies(svg_cell_counter *c, uint64_t *reads, uint64_t *mapped, uint64_t *assigned)
+{
+	if (!c || !reads || !mapped || !assigned) { svg_set_error("svg_cell_counter_tallies: NULL argument"); return SVG_E_ARG; }
+	// (the host copy is the device's after every call that succeeded)
+	const size_t k = (size_t)c->n_samples + 1;
+	memcpy(reads, c->cnt + CNT_HEAD, 8 * k);
+	memcpy(mapped, c->cnt + CNT_HEAD + k, 8 * k);
+	memcpy(assigned, c->cnt + CNT_HEAD + 2 * k, 8 * k);
 	return 0;
 }
 
 // ---- svg_cell_count_batch: the sink behind cell_align_run's chunks
 
+struct CellCountSink;
+static int count_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, const svg_packed_reads *barcodes, CellCountSink *sp,
+                     svg_cell_assigned *res);
+
 struct CellCountSink {
 	svg_cell_counter *c;
-	const svg_packed_reads *umis;
+	const svg_packed_reads *umis;    // svg_cell_count_batch: the UMIs and sample numbers from the host
 	const int32_t *sample_no;
+	const svg_reads *names;          // svg_cell_count_names_batch: both, and the barcodes, from the parse kernel
+	int mode, barcode_length;
+	CellNamesRun *nr;
 	void *d_ubases, *d_uxmask, *d_ustarts, *d_sample;
 	size_t held;
 	hipEvent_t ev[2];
@@ -427,9 +502,24 @@ static int sink_alloc(CellCountSink *s, void **p, size_t bytes)
 	return rc;
 }
 
-int cell_count_begin(CellCountSink *s, uint64_t n, hipStream_t st)
+const char *cell_count_who(CellCountSink *s) { return s->names ? "svg_cell_count_names_batch" : "svg_cell_count_batch"; }
+bool cell_count_has_names(CellCountSink *s) { return s->names != NULL; }
+
+static int sink_events(CellCountSink *s)
+{
+	if (s->c->h->timing)
+		for (int i = 0; i < 2; i++)
+			if (hipEventCreate(&s->ev[i]) != hipSuccess) { svg_set_error("%s: hipEventCreate failed", cell_count_who(s)); return SVG_E_DEVICE; }
+	return 0;
+}
+
+int cell_count_begin(CellCountSink *s, uint64_t n, uint64_t chunk, hipStream_t st)
 {
 	svg_cell_counter *c = s->c;
+	if (s->names) {
+		int rc = cell_names_begin(c->h, cell_count_who(s), s->names, s->mode, s->barcode_length, c->L, n, chunk, st, &s->nr);
+		return rc ? rc : sink_events(s);
+	}
 	const svg_packed_reads *u = s->umis;
 	uint64_t nbases = 0;
 	for (uint64_t i = 0; i < n; i++) {
@@ -456,9 +546,19 @@ int cell_count_begin(CellCountSink *s, uint64_t n, hipStream_t st)
 		svg_set_error("svg_cell_count_batch: upload failed");
 		return SVG_E_DEVICE;
 	}
-	if (c->h->timing)
-		for (int i = 0; i < 2; i++)
-			if (hipEventCreate(&s->ev[i]) != hipSuccess) { svg_set_error("svg_cell_count_batch: hipEventCreate failed"); return SVG_E_DEVICE; }
+	return sink_events(s);
+}
+
+// the parse kernel over the chunk's names, in front of the barcode kernel that reads its output
+int cell_count_parse(CellCountSink *s, uint64_t first_read, uint64_t k, const uint32_t **d_bc_bases, const uint32_t **d_bc_xmask)
+{
+	if (!s->nr) return 0;
+	int rc = cell_names_chunk(s->nr, first_read, k);
+	if (rc) return rc;
+	CellNamesView v;
+	cell_names_view(s->nr, &v);
+	*d_bc_bases = v.bc_bases;
+	*d_bc_xmask = v.bc_xmask;
 	return 0;
 }
 
@@ -469,9 +569,8 @@ int cell_count_chunk(CellCountSink *s, uint64_t first_read, uint64_t k, const sv
                      hipStream_t st)
 {
 	svg_cell_counter *c = s->c;
-	if (!n_genes) return 0;
 	unsigned long long n_now = 0;
-	if (hipMemcpy(&n_now, c->d_cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) { svg_set_error("svg_cell_count_batch: HIP error"); return SVG_E_DEVICE; }
+	if (hipMemcpy(&n_now, c->d_cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) { svg_set_error("%s: HIP error", cell_count_who(s)); return SVG_E_DEVICE; }
 	const uint64_t keep = c->cnt[0];
 	c->cnt[0] = n_now;               // (what counter_grow copies)
 	int rc = counter_grow(c, n_now + n_genes);
@@ -480,20 +579,30 @@ int cell_count_chunk(CellCountSink *s, uint64_t first_read, uint64_t k, const sv
 	ExpandParams ep;
 	memset(&ep, 0, sizeof ep);
 	ep.heads = d_heads; ep.hits = d_hits; ep.genes = d_genes; ep.bc = d_bc;
-	ep.sample = (const int32_t *)s->d_sample + first_read;
-	ep.ubases = (const uint32_t *)s->d_ubases;
-	ep.uxmask = (const uint32_t *)s->d_uxmask;
-	ep.ustarts = s->d_ustarts ? (const uint64_t *)s->d_ustarts + first_read : NULL;
-	ep.ustride = s->umis->stride;
-	ep.ubase0 = first_read * s->umis->stride;
+	if (s->nr) {
+		CellNamesView v;
+		cell_names_view(s->nr, &v);
+		cell_names_time(s->nr);
+		ep.sample = v.sample; ep.status = v.status;
+		ep.ubases = v.umi_bases; ep.uxmask = v.umi_xmask;
+		ep.ustride = SVG_CELL_NAME_STRIDE;
+	} else {
+		ep.sample = (const int32_t *)s->d_sample + first_read;
+		ep.ubases = (const uint32_t *)s->d_ubases;
+		ep.uxmask = (const uint32_t *)s->d_uxmask;
+		ep.ustarts = s->d_ustarts ? (const uint64_t *)s->d_ustarts + first_read : NULL;
+		ep.ustride = s->umis->stride;
+		ep.ubase0 = first_read * s->umis->stride;
+	}
 	ep.rec_base = rec_base; ep.gene_base = gene_base; ep.cap = c->cap;
 	ep.n = (uint32_t)k; ep.L = (uint32_t)c->L; ep.n_samples = c->n_samples;
 	ep.hi = c->d_hi; ep.lo = c->d_lo; ep.cnt = c->d_cnt;
 	if (s->ev[0]) hipEventRecord(s->ev[0], st);
-	hipLaunchKernelGGL(count_expand_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, ep);
+	if (n_genes) hipLaunchKernelGGL(count_expand_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, ep);
 	if (s->ev[0]) hipEventRecord(s->ev[1], st);
+	hipLaunchKernelGGL(count_tally_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, ep);
 	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-		svg_set_error("svg_cell_count_batch: HIP error %s", hipGetErrorString(hipGetLastError()));
+		svg_set_error("%s: HIP error %s", cell_count_who(s), hipGetErrorString(hipGetLastError()));
 		return SVG_E_DEVICE;
 	}
 	float ms = 0;
@@ -504,6 +613,7 @@ int cell_count_chunk(CellCountSink *s, uint64_t first_read, uint64_t k, const sv
 static void sink_free(CellCountSink *s)
 {
 	hipFree(s->d_ubases); hipFree(s->d_uxmask); hipFree(s->d_ustarts); hipFree(s->d_sample);
+	cell_names_end(s->nr);
 	for (int i = 0; i < 2; i++)
 		if (s->ev[i]) hipEventDestroy(s->ev[i]);
 	s->c->h->device_bytes -= s->held;
@@ -525,14 +635,45 @@ extern "C" int svg_cell_count_batch(svg_index *h, const svg_cell_align_params *p
 	CellCountSink s;
 	memset(&s, 0, sizeof s);
 	s.c = c; s.umis = umis; s.sample_no = sample_no;
+	return count_run(h, p, reads, barcodes, &s, res);
+}
+
+extern "C" int svg_cell_count_names_batch(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, const svg_reads *names,
+                                          int mode, svg_cell_counter *c, svg_cell_assigned *res)
+{
+	if (res) memset(res, 0, sizeof *res);
+	if (!h || !p || !reads || !c || !names) { svg_set_error("svg_cell_count_names_batch: NULL argument"); return SVG_E_ARG; }
+	if (c->h != h) { svg_set_error("svg_cell_count_names_batch: the counter belongs to another handle"); return SVG_E_ARG; }
+	if (names->n_reads != reads->n_reads) {
+		svg_set_error("svg_cell_count_names_batch: %llu names for %llu reads", (unsigned long long)names->n_reads, (unsigned long long)reads->n_reads);
+		return SVG_E_ARG;
+	}
+	const int bl = cell_assign_barcode_length(h);
+	if (!bl) { svg_set_error("svg_cell_count_names_batch: no whitelist (svg_cell_set_barcodes gives the barcode length)"); return SVG_E_ARG; }
+	if (cell_names_samples(h) > c->n_samples) {
+		svg_set_error("svg_cell_count_names_batch: a sample sheet of %d samples and a counter of %d", cell_names_samples(h), c->n_samples);
+		return SVG_E_ARG;
+	}
+	CellCountSink s;
+	memset(&s, 0, sizeof s);
+	s.c = c; s.names = names; s.mode = mode; s.barcode_length = bl;
+	return count_run(h, p, reads, NULL, &s, res);
+}
+
+// svg_cell_count_batch and svg_cell_count_names_batch behind their argument checks
+static int count_run(svg_index *h, const svg_cell_align_params *p, const svg_packed_reads *reads, const svg_packed_reads *barcodes, CellCountSink *sp,
+                     svg_cell_assigned *res)
+{
+	CellCountSink &s = *sp;
+	svg_cell_counter *c = s.c;
 	svg_cell_assigned tmp;
 	memset(&tmp, 0, sizeof tmp);
 	svg_cell_assigned *r = res ? res : &tmp;
 	int rc = cell_align_run(h, p, reads, &r->alns, barcodes, &r->hits, &r->cell_barcode_no, &s, res == NULL);
 	sink_free(&s);
-	if (!rc && hipMemcpy(c->cnt, c->d_cnt, 32, hipMemcpyDeviceToHost) != hipSuccess) { svg_set_error("svg_cell_count_batch: HIP error"); rc = SVG_E_DEVICE; }
+	if (!rc && hipMemcpy(c->cnt, c->d_cnt, c->cnt_bytes, hipMemcpyDeviceToHost) != hipSuccess) { svg_set_error("%s: HIP error", cell_count_who(&s)); rc = SVG_E_DEVICE; }
 	if (rc) {
-		hipMemcpy(c->d_cnt, c->cnt, 32, hipMemcpyHostToDevice);   // the counter as it was before the call
+		hipMemcpy(c->d_cnt, c->cnt, c->cnt_bytes, hipMemcpyHostToDevice);   // the counter as it was before the call
 		svg_cell_assign_free(r);
 		return rc;
 	}
@@ -608,6 +749,11 @@ extern "C" int svg_cell_counter_finish(svg_cell_counter *c, int want_entries, sv
 {
 	if (!c || !out) { svg_set_error("svg_cell_counter_finish: NULL argument"); return SVG_E_ARG; }
 	memset(out, 0, sizeof *out);
+	if (c->cnt[4]) {
+		svg_set_error("svg_cell_counter_finish: %llu read names refused (fewer than 3 fields, or a barcode or UMI past the name's end or with a character other than A/C/G/T/N; refused until svg_cell_counter_reset)",
+		              (unsigned long long)c->cnt[4]);
+		return SVG_E_ARG;
+	}
 	if (c->cnt[3]) {
 		svg_set_error("svg_cell_counter_finish: %llu observations with a sample, cell or gene number outside its key field (refused until svg_cell_counter_reset)",
 		              (unsigned long long)c->cnt[3]);

@@ -200,6 +200,8 @@ struct svg_index {
 	// svg_cell_count_batch and svg_cell_counter_finish under svg_set_timing (svg_cell_count.hip): expand, sort + run-length,
 	// step 1 lane kernel, step 1 wave kernel, step 2, count table
 	double cellcount_ms[6];
+	// svg_cell_set_samples' device image and the parse kernel's timing (svg_cell_names.hip)
+	struct svg_cellnames *cns;
 };
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { svg_set_error("HIP error %s at %s:%d", hipGetErrorString(_e), __FILE__, __LINE__); return SVG_E_DEVICE; } } while (0)
@@ -232,6 +234,8 @@ void svg_io_free(svg_index *h);
 void svg_long_ws_free(svg_index *h);
 // svg_cell_assign.hip
 void svg_cell_assign_ws_free(svg_index *h);
+// svg_cell_names.hip
+void svg_cell_names_ws_free(svg_index *h);
 
 // ---------------------------------------------------------------------------------------------
 // kernel parameters (passed by value)

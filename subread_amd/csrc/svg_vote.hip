@@ -3155,6 +3155,7 @@ extern "C" void svg_index_close(svg_index *h)
 	svg_io_free(h);
 	svg_long_ws_free(h);
 	svg_cell_assign_ws_free(h);
+	svg_cell_names_ws_free(h);
 	for (int s = 0; s < 3; s++) {
 		hipFree(h->d_prec[s]);
 		hipFree(h->d_lane[s]);
